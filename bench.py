@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: sequences/second of the GCRNN time-step recurrence on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|f32|f64] [--mode fwd|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|f32|f64] [--mode fwd|train] [--dump-outputs DIR]
 
 Workload = BASELINE.json configs[1]: synthetic k-step prediction, sparse SBM graph N=1000 (p_in 0.04,
 p_out 0.0025, nnz ~ 1e4), K=5 taps, T=32 steps, G=F=64 features, un-gated cell, h0 = 0. One "step" is one
@@ -26,6 +26,8 @@ import torch
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable copy rate)
 CFG = dict(N=1000, K=5, T=32, G=64, F=64)
+DUMP_SAMPLE = 1 << 21        # --dump-outputs: elements kept of a larger output (values + their flat indices <= 32 MB per output)
+DUMP_BUDGET = 64 << 20       # --dump-outputs: bytes of all files together
 
 
 def sbm_graph(N=1000, C=5, p_in=0.04, p_out=0.0025, seed=0, normalized=False):
@@ -123,6 +125,9 @@ def parse_args(argv=None):
                     'gloo only with --dry-run)')
     ap.add_argument('--dry-run', action='store_true', help='launcher / rendezvous / reduction plumbing only: no GPU, no kernels '
                     '(CPU test of the N > 1 entry)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed step computed '
+                    '(rank 0) as DIR/<name>.npy: fp32 (fp64 for fp64 runs), a fixed seeded sample of outputs above %d elements, '
+                    'at most 64 MB in all' % DUMP_SAMPLE)
     return ap.parse_args(argv)
 
 
@@ -160,6 +165,39 @@ def self_launch(args, argv):
         sys.stderr.write('bench.py: the %d-rank launch failed (exit %d): %s\n' % (args.gpus, rc, ' '.join(cmd)))
         sys.exit(rc if rc != 0 else 1)
     sys.exit(0)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: write {name: tensor} as DIR/<name>.npy in fp32 (fp64 tensors in fp64). A tensor of more than DUMP_SAMPLE
+    elements is written at DUMP_SAMPLE positions drawn without replacement by a fixed seed (sorted flat indices into the tensor's
+    shape, in DIR/<name>_index.npy as fp64), so that two builds run with the same arguments can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            pos = torch.from_numpy(np.stack(np.unravel_index(idx, tuple(t.shape)))).to(t.device)
+            files[name] = t[tuple(pos)].to(dt).cpu().numpy()
+            files[name + '_index'] = idx.astype(np.float64)
+        else:
+            files[name] = t.to(dt).cpu().numpy()
+    nbytes = sum(a.nbytes for a in files.values())
+    if nbytes > DUMP_BUDGET:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (budget %d)' % (nbytes, DUMP_BUDGET))
+    for name, a in files.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def train_outputs(loss, cell):
+    """What one optimiser step hands its caller: the loss, every parameter's gradient and the updated parameters."""
+    out = {'loss': loss}
+    for n, p in cell.named_parameters():
+        if p.grad is not None:
+            out['grad.' + n] = p.grad
+        out['param.' + n] = p
+    return out
 
 
 def dry_run(args, rank, world):
@@ -207,6 +245,8 @@ def main(argv=None):
                  '`python -m torch.distributed.run --nnodes=1 --nproc-per-node %d --master-addr 127.0.0.1 bench.py --gpus %d`'
                  % (args.gpus, world, args.gpus, args.gpus, args.gpus))
     if args.dry_run:
+        if args.dump_outputs:
+            sys.exit('bench.py: --dry-run computes nothing to dump')
         return dry_run(args, rank, world)
     if args.backend != 'nccl':
         sys.exit('bench.py: --backend gloo is for --dry-run only (the product has no CPU path)')
@@ -237,9 +277,11 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0   # MI355X_MICROARCH.md: ~2.5 PF dense bf16
 MFMA_F64_PEAK_TFLOPS = 78.6      # v_mfma_f64_16x16x4: 64 cycles per 16x16x4 MFMA per SIMD on MI355X = half the fp32 matrix rate
 
 
-def timed_steps(ctx, step):
+def timed_steps(ctx, step, reset=None):
     """W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize on both sides; wall = MAX over ranks.
-    Returns (wall seconds, device milliseconds between HIP events on the current stream)."""
+    `reset`, given when a step changes state (an optimiser step), runs after the settle phase and before the warm-up steps: the number
+    of settle steps depends on timing, so without it the last timed step would see other inputs from run to run.
+    Returns (wall seconds, device milliseconds between HIP events on the current stream, what the last timed step returned)."""
     args, dev, dist_on = ctx['args'], ctx['dev'], ctx['dist_on']
 
     def sync():
@@ -274,6 +316,8 @@ def timed_steps(ctx, step):
         for _ in range(n):        # queued back to back (no synchronisation inside: the load must be continuous), straight into the warm-up steps
             step()
         ctx['settle_steps'] = n + 2
+    if reset is not None:
+        reset()                   # (device-side copies queued behind the settle steps: no idle gap)
     for _ in range(args.warmup):
         step()
     sync()
@@ -287,8 +331,10 @@ def timed_steps(ctx, step):
     t0 = time.perf_counter()
     ev0.record()
     trace = [] if os.environ.get('GCRNN_BENCH_TRACE') else None       # diagnosis only: per-step host time and a device event
+    last = None
     for _ in range(args.steps):
-        step()
+        del last                  # the previous step's output is freed before the next step allocates its own, as when it is not kept
+        last = step()
         if trace is not None:
             e = torch.cuda.Event(enable_timing=True)
             e.record()
@@ -306,7 +352,7 @@ def timed_steps(ctx, step):
         tw = torch.tensor([wall], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tw, op=torch.distributed.ReduceOp.MAX)
         wall = float(tw.item())
-    return wall, dev_ms
+    return wall, dev_ms, last
 
 
 def base_line(ctx, value, wall, workload, B, extra=None):
@@ -390,8 +436,15 @@ def run_cfg2(ctx):
         opt.step()
         return loss
 
-    wall, dev_ms = timed_steps(ctx, step)
+    reset = None
+    if opt is not None:
+        initial = opt.state_dict()
+        reset = lambda: opt.load_state_dict(initial)      # noqa: E731
+    wall, dev_ms, last = timed_steps(ctx, step, reset)
     value = world * B * args.steps / wall
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(last, cell) if opt is not None else {'H': last})
+    del last
 
     # ---- dominant kernel: the fused step kernel, timed live with HIP events on the stream it is launched on ----
     kern, native = None, None
@@ -906,8 +959,11 @@ def run_cfg5(ctx):
         with torch.no_grad():
             return cell(X, h0)
 
-    wall, dev_ms = timed_steps(ctx, step)
+    wall, dev_ms, last = timed_steps(ctx, step)
     value = world * B * args.steps / wall
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'H': last})
+    del last
     # dominant kernel: spmm_stream_kernel, one launch = one hop of one time step for the whole batch; timed live with HIP events
     acc = torch.randn(1, N, B, F, device=dev).to(dt)
     dst = torch.randn(1, N, B, F, device=dev).to(dt)
@@ -994,8 +1050,11 @@ def run_cfg4(ctx):
         with torch.no_grad():
             return cell(X, h0)
 
-    wall, dev_ms = timed_steps(ctx, step)
+    wall, dev_ms, last = timed_steps(ctx, step)
     value = world * B * args.steps / wall
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'H': last})
+    del last
     if rank != 0:
         return None
     nnz = int(np.count_nonzero(S))

@@ -734,6 +734,37 @@ def test_bench_lines_run(dev, argv):
     assert out['value'] > 0 and out['n_gpus'] == 1 and 'workload' in out['config']
 
 
+@pytest.mark.parametrize('argv', [['--batch', '16', '--no-secondary'], ['--batch', '8', '--mode', 'train', '--time-gating']])
+def test_bench_dump_outputs_repeat_bit_for_bit(dev, argv, tmp_path):
+    """`--dump-outputs DIR` writes what the last of the --steps timed steps computed; two runs with the same arguments write the same
+    arrays bit for bit (the training line restores the initial parameters and optimiser state behind the timing-dependent settle
+    phase), and the line reports --steps and its ms_per_step."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    dumps = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+                            '--dump-outputs', str(tmp_path / run)] + argv, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+        assert out['steps'] == 3 and out['ms_per_step'] > 0
+        names = sorted(os.listdir(tmp_path / run))
+        dumps.append({f: np.load(tmp_path / run / f) for f in names})
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dumps[-1].values())
+        assert sum(os.path.getsize(tmp_path / run / f) for f in names) <= 64 << 20
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    if '--mode' in argv:
+        assert 'loss.npy' in a and 'grad.weight_A.npy' in a and any(f.startswith('param.MLP_forget') for f in a)
+    else:
+        assert a['H.npy'].shape == a['H_index.npy'].shape and float(np.abs(a['H.npy']).max()) > 0
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+
+
 def test_streaming_spmm_edge_cases(dev):
     """Empty graph, a single row, rows narrower than the narrowest piece, an odd row length (scalar fallback incl. the tanh
     epilogue), a destination count that is not a multiple of the rows per workgroup."""

@@ -158,6 +158,31 @@ def test_bench_self_launches_its_ranks():
     assert r.returncode != 0 and 'torch.distributed.run' in r.stderr
 
 
+def test_bench_dump_outputs_is_seeded_typed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole in fp32 (fp64 kept), a large one as the same seeded sample in every
+    call with its flat indices beside it, and a dump over the 64 MB budget is refused before anything is written."""
+    import bench
+    n = 3 * bench.DUMP_SAMPLE
+    big = torch.arange(n, dtype=torch.float64).reshape(3, 16, -1)
+    arrays = {'H': big, 'loss': torch.tensor(0.5, dtype=torch.bfloat16), 'grad.w': torch.ones(4, 5, dtype=torch.bfloat16)}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['H.npy', 'H_index.npy', 'grad.w.npy', 'loss.npy'] and sorted(os.listdir(tmp_path / 'b')) == names
+    got = {f[:-4]: np.load(tmp_path / 'a' / f) for f in names}
+    for f in names:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / 'b' / f))
+    assert got['H'].dtype == np.float64 and got['loss'].dtype == np.float32 and got['grad.w'].dtype == np.float32
+    assert got['loss'].shape == () and float(got['loss']) == 0.5 and got['grad.w'].shape == (4, 5)
+    idx = got['H_index']
+    assert idx.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(got['H'], idx)                     # the value at flat position i of `big` is i
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in names) <= bench.DUMP_BUDGET
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'c'), {'H%d' % i: big for i in range(3)})
+    assert not os.listdir(tmp_path / 'c')
+
+
 class TinyGCRNN(torch.nn.Module):
     """CPU stand-in with the surface MultipleModels touches (archit.stateGCRNN.weight_A for device / dtype, archit(x, h0))."""
 
@@ -170,7 +195,7 @@ class TinyGCRNN(torch.nn.Module):
         return torch.tanh(x @ self.stateGCRNN.weight_A) + 0.0 * h0.sum()
 
 
-def harness_worker(rank, world, port, ret):
+def harness_worker(rank, world, port, ret, save_dir):
     """MultipleModels with nTrain % batchSize < world: the last global batch has ONE sample, so rank 1's shard is empty. It
     must still join every collective (zeros, weight 0) and end with the same parameters as rank 0 -- and as a single process
     that trains on the whole batches (the empty slice used to die in `.view(0, T, -1)` while rank 0 hung)."""
@@ -186,7 +211,7 @@ def harness_worker(rank, world, port, ret):
     def build():
         torch.manual_seed(5)
         m = TinyGCRNN(N)
-        return m, TrainableModel(m, torch.nn.functional.l1_loss, FlatAdam(m.parameters(), lr=1e-2), 'TinyGCRNN', '/tmp')
+        return m, TrainableModel(m, torch.nn.functional.l1_loss, FlatAdam(m.parameters(), lr=1e-2), 'TinyGCRNN', save_dir)
 
     # the optimiser (and with it the flat gradient buffer) is built BEFORE the process group exists: the world size must be read late
     mdl, tm = build()
@@ -206,12 +231,12 @@ def harness_worker(rank, world, port, ret):
     ret[rank] = bool(ok)
 
 
-def test_multiple_models_survives_an_empty_shard():
+def test_multiple_models_survives_an_empty_shard(tmp_path):
     world = 2
     port = free_port()
     mgr = mp.Manager()
     ret = mgr.dict()
-    mp.spawn(harness_worker, args=(world, port, ret), nprocs=world, join=True)
+    mp.spawn(harness_worker, args=(world, port, ret, str(tmp_path)), nprocs=world, join=True)
     assert all(ret[r] for r in range(world)), dict(ret)
 
 
