@@ -9,6 +9,11 @@ SYNTHETIC: a pulse is released at a random station and spreads over the 59-stati
 stations) of the source. Same tensor shapes and model as the driver: x is B x T x 1 x 59, 11 classes.
 
     python examples/epicenter_estimation.py [--seq 200] [--taps 3] [--steps 600] [--lr 5e-3] [--time-gating] [--dtype f64]
+    python examples/epicenter_estimation.py --models Sel,GCRNNGNN,TimeGCRNNGNN
+
+--models picks the driver's other models (epicenterEstimation.py:150-153, 180-196, 258-280): 'Sel' = SelectionGNN([T, 21], [taps],
+ReLU, NoPool, MLP [11]) on the window's T samples as node features, 'GCRNNGNN' / 'TimeGCRNNGNN' = the gated GCRNN with a
+Selection-GNN head [F, 1], K = taps, MLP [11], final ReLU. Default: the MLP-head GCRNN ('TimeGCRNNMLP' with --time-gating).
 
 Measured on one MI355X (fp64, batch 100): T=200 3.6 ms per optimiser step, 84 % test accuracy after 600 steps (chance 9 %);
 T=50 1.1 ms per step, 99.8 %. The time-gated variant trains at 2.0 ms per step (T=50) but needs the reference's
@@ -24,6 +29,7 @@ import numpy as np
 import torch
 
 import gated_gcrnns_amd.Modules.architectures as archit
+import gated_gcrnns_amd.Utils.graphML as gml
 from gated_gcrnns_amd.Modules.train_rnn import train_step
 from gated_gcrnns_amd.Utils import dataTools
 
@@ -45,6 +51,9 @@ def synthetic_waves(S, n, T, regions, rng):
     return x, regions[src]
 
 
+MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN')
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--seq', type=int, default=200)
@@ -55,7 +64,11 @@ def main(argv=None):
     ap.add_argument('--lr', type=float, default=5e-3, help='the reference driver uses 1e-3 over many epochs')
     ap.add_argument('--time-gating', action='store_true')
     ap.add_argument('--dtype', default='f64', choices=['f32', 'f64'])
+    ap.add_argument('--models', default=None, help='comma-separated, of ' + ','.join(MODELS) + ' (default: one MLP-head GCRNN)')
     args = ap.parse_args(argv)
+    names = args.models.split(',') if args.models else ['TimeGCRNNMLP' if args.time_gating else 'GCRNNMLP']
+    if any(n not in MODELS for n in names):
+        ap.error('unknown model in %s; choose from %s' % (args.models, ','.join(MODELS)))
     dt = torch.float64 if args.dtype == 'f64' else torch.float32
     torch.set_default_dtype(dt)                                      # the reference driver runs in float64
     dev = torch.device('cuda:0')
@@ -68,28 +81,44 @@ def main(argv=None):
     xtr, ytr = synthetic_waves(S, 20 * args.batch, args.seq, regions, rng)
     xte, yte = synthetic_waves(S, 5 * args.batch, args.seq, regions, rng)
     to_x = lambda a: torch.tensor(a, dtype=dt, device=dev).unsqueeze(2)              # B x T x 1 x N
-    model = archit.GatedGCRNNforClassification(1, args.features, args.taps, args.taps, torch.tanh, torch.nn.ReLU, [11], S, True,
-                                               time_gating=args.time_gating, spatial_gating=None).to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999))
-    ce = torch.nn.CrossEntropyLoss()
     xtr_d, ytr_d = to_x(xtr), torch.tensor(ytr, device=dev)
-    times, first, losses = [], None, []
-    for it in range(args.steps):
-        idx = torch.tensor(rng.choice(xtr.shape[0], args.batch, replace=False), device=dev)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        loss, _ = train_step(model, ce, opt, xtr_d[idx], ytr_d[idx], args.features)
-        torch.cuda.synchronize(); times.append(time.perf_counter() - t0)
-        first = float(loss) if first is None else first
-        losses.append(float(loss))
-    with torch.no_grad():
-        xe = to_x(xte)
-        h0 = torch.zeros(xe.shape[0], args.features, N, dtype=dt, device=dev)
-        acc = float((model(xe, h0).argmax(dim=1).cpu() == torch.tensor(yte)).double().mean())
-    ms = 1e3 * float(np.median(times[3:]))
-    print('%sGCRNN classification N=%d T=%d K=%d F=%d %s: loss %.3f -> %.3f, test accuracy %.3f (chance %.3f), '
-          'median %.2f ms/step (%.0f seq/s)' % ('Time' if args.time_gating else '', N, args.seq, args.taps, args.features,
-                                               args.dtype, first, float(loss), acc, 1 / 11, ms, args.batch / (ms / 1e3)))
-    return {'loss': losses, 'accuracy': acc, 'ms_per_step': ms}
+    xe = to_x(xte)
+    results = {}
+    for name in names:
+        torch.manual_seed(0)
+        gnn = name == 'Sel'
+        if gnn:
+            model = archit.SelectionGNN([args.seq, 21], [args.taps], True, torch.nn.ReLU, [N], gml.NoPool, [1], [11], S).to(dev)
+            fwd = lambda a, x: a(x.squeeze(2))                           # the T samples of a window are the node features
+        else:
+            tg = name.startswith('Time')
+            head = dict(finalNonlinearity=torch.nn.ReLU, dimNodeSignals=[args.features, 1], nFilterTaps=[args.taps], nSelectedNodes=[N],
+                        poolingFunction=gml.NoPool, poolingSize=[1]) if name.endswith('GNN') else {}
+            model = archit.GatedGCRNNforClassification(1, args.features, args.taps, args.taps, torch.tanh, torch.nn.ReLU, [11], S, True,
+                                                       time_gating=tg, spatial_gating=None, **head).to(dev)
+            fwd = None
+        opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999))
+        ce = torch.nn.CrossEntropyLoss()
+        times, first, losses = [], None, []
+        for it in range(args.steps):
+            idx = torch.tensor(rng.choice(xtr.shape[0], args.batch, replace=False), device=dev)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            loss, _ = train_step(model, ce, opt, xtr_d[idx], ytr_d[idx], args.features, forward=fwd)
+            torch.cuda.synchronize(); times.append(time.perf_counter() - t0)
+            first = float(loss) if first is None else first
+            losses.append(float(loss))
+        with torch.no_grad():
+            if gnn:
+                logits = model(xe.squeeze(2))
+            else:
+                logits = model(xe, torch.zeros(xe.shape[0], args.features, N, dtype=dt, device=dev))
+            acc = float((logits.argmax(dim=1).cpu() == torch.tensor(yte)).double().mean())
+        ms = 1e3 * float(np.median(times[3:]))
+        print('%s classification N=%d T=%d K=%d F=%d %s: loss %.3f -> %.3f, test accuracy %.3f (chance %.3f), '
+              'median %.2f ms/step (%.0f seq/s)' % (name, N, args.seq, args.taps, args.features, args.dtype, first, float(loss), acc,
+                                                   1 / 11, ms, args.batch / (ms / 1e3)))
+        results[name] = {'loss': losses, 'accuracy': acc, 'ms_per_step': ms}
+    return results[names[0]] if len(names) == 1 else results
 
 
 if __name__ == '__main__':

@@ -8,6 +8,9 @@
 Defaults follow the reference driver (N=80 SBM 0.8/0.2, 5 taps, K=seqLen=5, F=20, batch 100, Adam 1e-3). --dtype bf16 feeds
 bf16 batches to fp32 master weights: all four variants (un-gated, time-, node- and edge-gated) then train on the fused kernels
 (N <= 1024, F in {32, 64}; other shapes: composed path in fp32). --sparse draws the BASELINE configs[1] graph (mean degree ~10).
+--models also accepts the driver's GNN models: 'Sel' (SelectionGNN([1, 8, 1], [10, 10], ReLU, NoPool), every time step a sample,
+kStepPredGRNNs.py:197) and 'GCRNNGNN' / 'TimeGCRNNGNN' (a Selection-GNN head [F, 1], K = taps, final ReLU; the driver's [5, 1]
+with F = 20 fails the reference's own shape assert).
 """
 import argparse
 import os
@@ -19,9 +22,13 @@ import numpy as np
 import torch
 
 import gated_gcrnns_amd.Modules.architectures as archit
+import gated_gcrnns_amd.Utils.graphML as gml
 from gated_gcrnns_amd.Modules.train_rnn import MultipleModels, TrainableModel
 from gated_gcrnns_amd.Utils import dataTools, miscTools
 from gated_gcrnns_amd.optim import FlatAdam
+
+
+MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'NodeGCRNNMLP', 'EdgeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN')
 
 
 def main(argv=None):
@@ -36,11 +43,15 @@ def main(argv=None):
     ap.add_argument('--ntrain', type=int, default=2000)
     ap.add_argument('--dtype', default='f64', choices=['f32', 'f64', 'bf16'])
     ap.add_argument('--sparse', action='store_true', help='SBM with p_in 0.04 / p_out 0.0025 (BASELINE configs[1]) instead of 0.8 / 0.2')
-    ap.add_argument('--models', default='GCRNNMLP,TimeGCRNNMLP,NodeGCRNNMLP,EdgeGCRNNMLP')
+    ap.add_argument('--models', default='GCRNNMLP,TimeGCRNNMLP,NodeGCRNNMLP,EdgeGCRNNMLP',
+                    help='comma-separated, of ' + ','.join(MODELS))
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--optim', default='flat', choices=['flat', 'torch'], help='flat: optim.FlatAdam (one kernel over the flat '
                     'parameter / gradient buffers); torch: torch.optim.Adam as in the reference driver')
     args = ap.parse_args(argv)
+    unknown = [n for n in args.models.split(',') if n not in MODELS]
+    if unknown:
+        ap.error('unknown model(s) %s; choose from %s' % (','.join(unknown), ','.join(MODELS)))
     dt = torch.float64 if args.dtype == 'f64' else torch.float32       # parameter dtype (bf16: fp32 master weights)
     data_dt = torch.bfloat16 if args.dtype == 'bf16' else dt
     torch.set_default_dtype(dt)                                   # the reference driver runs in float64 (line 44)
@@ -64,6 +75,19 @@ def main(argv=None):
         else:
             opt = torch.optim.Adam(m.parameters(), lr=1e-3, betas=(0.9, 0.999))
         models[name] = TrainableModel(m, miscTools.batchTimeL1Loss, opt, name, saveDir)
+    for name in args.models.split(','):
+        if name == 'Sel':
+            m = archit.SelectionGNN([1, 8, 1], [10, 10], True, torch.nn.ReLU, [args.nodes] * 2, gml.NoPool, [1, 1], [], S)
+        elif name in ('GCRNNGNN', 'TimeGCRNNGNN'):
+            m = archit.GatedGCRNNforRegression(1, args.features, args.taps, args.taps, torch.tanh, torch.nn.ReLU, [], S, True,
+                                               name == 'TimeGCRNNGNN', None, 'oneMlp', torch.nn.ReLU, [args.features, 1], [args.taps],
+                                               [args.nodes], gml.NoPool, [1])
+        else:
+            continue
+        m = m.to(dev)
+        opt = FlatAdam(m.parameters(), lr=1e-3, betas=(0.9, 0.999)) if args.optim == 'flat' else \
+            torch.optim.Adam(m.parameters(), lr=1e-3, betas=(0.9, 0.999))
+        models[name] = TrainableModel(m, miscTools.batchTimeL1Loss, opt, name, saveDir)
     xT, yT = data.getSamples('train')
     xV, yV = data.getSamples('valid')
     out = MultipleModels(models, xT, yT, xV, yV, args.epochs, args.batch, data.seqLen, args.features,
@@ -75,8 +99,12 @@ def main(argv=None):
     for name, tm in models.items():
         tm.load('Best')
         with torch.no_grad():
-            h0 = torch.zeros(xE.shape[0], args.features, args.nodes, device=dev, dtype=data_dt)
-            score = float(data.evaluate(tm.archit(xE, h0).to(yE.dtype), yE))
+            if name == 'Sel':                                             # every time step a sample (reference train_rnn.py:243)
+                yS = tm.archit(xE.reshape(-1, 1, args.nodes).to(dt)).unsqueeze(1)
+                score = float(data.evaluate(yS.to(yE.dtype), yE.reshape(-1, 1, args.nodes)))
+            else:
+                h0 = torch.zeros(xE.shape[0], args.features, args.nodes, device=dev, dtype=data_dt)
+                score = float(data.evaluate(tm.archit(xE, h0).to(yE.dtype), yE))
         t = np.median(out['timeTrain'][name])
         print('%-14s test RMSE-metric %.4f   loss %.4f -> %.4f   median %.1f ms/batch (%.0f seq/s)' % (
             name, score, out['lossTrain'][name][0], out['lossTrain'][name][-1], 1e3 * t, args.batch / t))

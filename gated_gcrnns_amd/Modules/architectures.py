@@ -2,9 +2,10 @@
 Modules/architectures.py:1405-1859 for the hot path).
 
 Same positional constructor signatures, attribute names and state_dict keys
-(`stateGCRNN.*`, `outputNN.<i>.*`). Only the MLP output heads are provided (the
-drivers' 'multipMlp' / 'oneMlp'); the reference's optional Selection/Aggregation-GNN
-heads belong to model families outside the hot path.
+(`stateGCRNN.*`, `outputNN.<i>.*`). Output heads: the MLPs (the drivers' 'multipMlp' /
+'oneMlp') and the Selection GNN (reference architectures.py:10-177, also stand-alone as
+`SelectionGNN`) without node-selecting pooling; every graph-filter layer of it runs as one
+HIP launch per pass (ops.graph_filter_layer). Aggregation-GNN heads are not provided.
 """
 import numpy as np
 import torch
@@ -53,10 +54,76 @@ def _build_mlp(dimInputMLP, dimLayersMLP, sigma2, sigma3, bias):
     return nn.Sequential(*fc)
 
 
+_FUSED_ACTIVATIONS = {nn.ReLU: 'relu', nn.Tanh: 'tanh', nn.Sigmoid: 'sigmoid'}
+
+
+class SelectionGNN(nn.Module):
+    """Selection GNN (reference architectures.py:10-177): L graph-filter layers (GraphFilter, sigma, pooling) and an MLP on the
+    flattened output. Same signature, asserts, state_dict keys (`GFL.<3l>.*`, `MLP.<i>.*`) and seeded initialisation.
+
+    forward(x: B x F[0] x N) -> B x dimLayersMLP[-1] (B x F[-1]*N without an MLP). Each layer is ops.graph_filter_layer on the
+    GraphFilter's live parameters with sigma fused when it is ReLU / Tanh / Sigmoid (other modules are applied after it).
+    Only NoPool with nSelectedNodes[l] = N is provided: pooling that drops nodes raises NotImplementedError.
+    """
+
+    def __init__(self, dimNodeSignals, nFilterTaps, bias, nonlinearity, nSelectedNodes, poolingFunction, poolingSize,
+                 dimLayersMLP, GSO):
+        super().__init__()
+        assert len(dimNodeSignals) == len(nFilterTaps) + 1
+        assert len(nSelectedNodes) == len(nFilterTaps)
+        assert len(poolingSize) == len(nFilterTaps)
+        S = _as_gso_tensor(GSO)
+        self.L = len(nFilterTaps)
+        self.F = dimNodeSignals
+        self.K = nFilterTaps
+        self.E = int(S.shape[0])
+        self.N = [int(S.shape[1])] + nSelectedNodes
+        if poolingFunction is not gml.NoPool or any(n != self.N[0] for n in nSelectedNodes):
+            raise NotImplementedError('SelectionGNN: pooling that selects nodes (MaxPoolLocal, nSelectedNodes != N) is not implemented; '
+                                      'use poolingFunction=NoPool with nSelectedNodes=[N] * L')
+        self.bias = bias
+        self.register_buffer('S', S, persistent=False)            # moved by .to(); not in state_dict (as the reference)
+        self.sigma = nonlinearity
+        self.rho = poolingFunction
+        self.alpha = poolingSize
+        self.dimLayersMLP = dimLayersMLP
+        gfl = []
+        for l in range(self.L):                                   # reference :114-129, same construction order
+            gfl.append(gml.GraphFilter(self.F[l], self.F[l + 1], self.K[l], self.E, self.bias))
+            gfl[3 * l].addGSO(self.S)
+            gfl.append(self.sigma())
+            gfl.append(self.rho(self.N[l], self.N[l + 1], self.alpha[l]))
+            gfl[3 * l + 2].addGSO(self.S)
+        self.GFL = nn.Sequential(*gfl)
+        fc = []
+        if len(self.dimLayersMLP) > 0:                            # reference :133-153
+            fc.append(nn.Linear(self.N[-1] * self.F[-1], dimLayersMLP[0], bias=self.bias))
+            for l in range(len(dimLayersMLP) - 1):
+                fc.append(self.sigma())
+                fc.append(nn.Linear(dimLayersMLP[l], dimLayersMLP[l + 1], bias=self.bias))
+        self.MLP = nn.Sequential(*fc)
+
+    def forward(self, x):
+        assert len(x.shape) == 3
+        batchSize = x.shape[0]
+        assert x.shape[1] == self.F[0]
+        assert x.shape[2] == self.N[0]
+        y = x
+        for l in range(self.L):
+            gf, sigma, pool = self.GFL[3 * l], self.GFL[3 * l + 1], self.GFL[3 * l + 2]
+            act = _FUSED_ACTIVATIONS.get(type(sigma))
+            y = ops.graph_filter_layer(y, gf.weight, gf.bias, gf.graph, act)
+            if act is None:
+                y = sigma(y)
+            y = pool(y)
+        y = y.reshape(batchSize, self.F[-1] * self.N[-1])
+        return self.MLP(y)
+
+
 class _GatedGCRNNBase(nn.Module):
     def _init_state(self, inFeatures, stateFeatures, inputFilterTaps, stateFilterTaps, stateNonlinearity,
                     outputNonlinearity, dimLayersMLP, GSO, bias, time_gating, spatial_gating, finalNonlinearity,
-                    dimNodeSignals, nFilterTaps):
+                    dimNodeSignals, nFilterTaps, nSelectedNodes=None, poolingFunction=None, poolingSize=None, maxN=None):
         S = _as_gso_tensor(GSO)
         self.F_i, self.K_i = inFeatures, inputFilterTaps
         self.F_h, self.K_h = stateFeatures, stateFilterTaps
@@ -74,9 +141,21 @@ class _GatedGCRNNBase(nn.Module):
         self.sigma3 = finalNonlinearity
         self.F_o = dimNodeSignals
         self.K_o = nFilterTaps
-        if dimNodeSignals is not None or nFilterTaps is not None:
-            raise NotImplementedError('GNN output heads (SelectionGNN / AggregationGNN) are outside the GCRNN hot path; '
-                                      'use the MLP heads (dimNodeSignals=None, nFilterTaps=None)')
+        self.nSelectedNodes = nSelectedNodes
+        self.rho = poolingFunction
+        self.alpha = poolingSize
+        self.maxN = maxN
+        self.gnn_head = not (dimNodeSignals is None and nFilterTaps is None)
+        if self.gnn_head and nSelectedNodes is None and poolingFunction is not gml.NoPool:      # reference :1571-1586
+            raise NotImplementedError('AggregationGNN output heads are not implemented; give nSelectedNodes and poolingFunction=NoPool '
+                                      'for a Selection-GNN head, or use the MLP heads (dimNodeSignals=None, nFilterTaps=None)')
+
+    def _selection_head(self, GSO):
+        """outputNN of the Selection-GNN branch (reference :1588-1604 / :1823-1839): SelectionGNN + the final nonlinearity."""
+        sel = [SelectionGNN(self.F_o, self.K_o, self.bias, self.sigma2, self.nSelectedNodes, self.rho, self.alpha, self.dimLayersMLP, GSO)]
+        if self.sigma3 is not None:
+            sel.append(self.sigma3())
+        return nn.Sequential(*sel)
 
 
 class GatedGCRNNforRegression(_GatedGCRNNBase):
@@ -92,14 +171,22 @@ class GatedGCRNNforRegression(_GatedGCRNNBase):
         super().__init__()
         self._init_state(inFeatures, stateFeatures, inputFilterTaps, stateFilterTaps, stateNonlinearity,
                          outputNonlinearity, dimLayersMLP, GSO, bias, time_gating, spatial_gating,
-                         finalNonlinearity, dimNodeSignals, nFilterTaps)
+                         finalNonlinearity, dimNodeSignals, nFilterTaps, nSelectedNodes, poolingFunction, poolingSize, maxN)
         self.mlpType = mlpType
+        if self.gnn_head:
+            self.outputNN = self._selection_head(self.S)
+            return
         dimInputMLP = self.N * self.F_h if mlpType == 'oneMlp' else self.F_h     # reference :1545-1554
         assert mlpType in ('oneMlp', 'multipMlp')
         self.outputNN = _build_mlp(dimInputMLP, self.dimLayersMLP, self.sigma2, self.sigma3, self.bias)
 
     def forward(self, x, h0):
         batchSize, seqLength = x.shape[0], x.shape[1]
+        if self.gnn_head:
+            # the Selection-GNN head on all B*T states (reference :1630-1632): H [B][T][F_h][N] is already its [items][F][N] input
+            H = self.stateGCRNN(x, h0)
+            flatY = self.outputNN(H.reshape(-1, self.F_h, self.N))
+            return flatY.reshape(batchSize, seqLength, -1).unsqueeze(2)
         if self.mlpType == 'multipMlp' and not torch.is_grad_enabled() and len(self.outputNN) == 1 and \
                 isinstance(self.outputNN[0], nn.Linear) and self.outputNN[0].out_features == 1:
             # inference with the drivers' head (dimLayersMLP = [1]): fused onto the cell's h_t store, H is never materialised
@@ -133,10 +220,15 @@ class GatedGCRNNforClassification(_GatedGCRNNBase):
         super().__init__()
         self._init_state(inFeatures, stateFeatures, inputFilterTaps, stateFilterTaps, stateNonlinearity,
                          outputNonlinearity, dimLayersMLP, GSO, bias, time_gating, spatial_gating,
-                         finalNonlinearity, dimNodeSignals, nFilterTaps)
-        self.outputNN = _build_mlp(self.N * self.F_h, self.dimLayersMLP, self.sigma2, self.sigma3, self.bias)
+                         finalNonlinearity, dimNodeSignals, nFilterTaps, nSelectedNodes, poolingFunction, poolingSize, maxN)
+        if self.gnn_head:
+            self.outputNN = self._selection_head(self.S)
+        else:
+            self.outputNN = _build_mlp(self.N * self.F_h, self.dimLayersMLP, self.sigma2, self.sigma3, self.bias)
 
     def forward(self, x, h0):
         H = self.stateGCRNN(x, h0, last_only=not torch.is_grad_enabled())     # inference: only the last state is materialised
         h = H.select(1, -1)                                          # reference :1844
+        if self.gnn_head:
+            return self.outputNN(h)                                  # reference :1848-1849
         return self.outputNN(_to_param_dtype(h, self.outputNN).reshape(-1, self.F_h * self.N))

@@ -29,12 +29,14 @@ def batch_partition(nTrain, batchSize):
     return sizes, np.cumsum([0] + sizes).tolist()
 
 
-def train_step(archit, loss_fn, optim, x, y, stateFeat, sync=None, weight=None):
+def train_step(archit, loss_fn, optim, x, y, stateFeat, sync=None, weight=None, forward=None):
     """One optimiser step on a batch x, y: B x T x 1 x N (already on the device). Returns (loss, yHat).
     weight: this rank's share of the global batch (local / global); the flat all-reduce sums the ranks' mean-loss
     gradients with these weights = the gradient of the global-batch mean. A rank whose shard is empty (global batch
-    smaller than the world) contributes zeros and still joins the collective."""
-    B, N = x.shape[0], x.shape[3]
+    smaller than the world) contributes zeros and still joins the collective.
+    forward: yHat = forward(archit, x) for models without a state (the GNNs, reference train_rnn.py:264-267); default
+    archit(x, h0) with h0 = 0."""
+    B = x.shape[0]
     if sync is None and hasattr(optim, 'sync'):
         sync_z = optim.sync                      # optim.FlatAdam: the gradients live in its flat buffer
     else:
@@ -45,8 +47,11 @@ def train_step(archit, loss_fn, optim, x, y, stateFeat, sync=None, weight=None):
         archit.zero_grad()
     loss, yHat = None, None
     if B > 0:
-        h0 = torch.zeros(B, stateFeat, N, dtype=x.dtype, device=x.device)
-        yHat = archit(x, h0)
+        if forward is not None:
+            yHat = forward(archit, x)
+        else:
+            h0 = torch.zeros(B, stateFeat, x.shape[3], dtype=x.dtype, device=x.device)
+            yHat = archit(x, h0)
         loss = loss_fn(yHat, y)
         loss.backward()
     if sync is not None:
@@ -75,9 +80,29 @@ class TrainableModel(object):
         self.optim.load_state_dict(torch.load(os.path.join(d, self.name + 'Optim' + label + '.ckpt')))
 
 
+def _is_gcrnn(name):
+    return 'GCRNN' in name or 'gcrnn' in name or 'GCRnn' in name          # reference dispatches on the name (train_rnn.py:253)
+
+
+def _is_rnn(name):
+    return 'RNN' in name or 'rnn' in name or 'Rnn' in name                 # reference train_rnn.py:237
+
+
+def _gnn_forward(archit, x):
+    """The reference's non-recurrent branch (train_rnn.py:264-267): x (B*T) x 1 x N -> archit(x) -> (B*T) x 1 x out."""
+    return archit(x).unsqueeze(1)
+
+
+def _first_parameter(archit):
+    return archit.stateGCRNN.weight_A if hasattr(archit, 'stateGCRNN') else next(archit.parameters())
+
+
 def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSize, seqLen, stateFeat,
                    evaluate, validationInterval=5, rank=0, world=1, doPrint=False, rng=None, dataType=None):
-    """Train every model of `modelsDict` (name -> TrainableModel, names containing 'GCRNN') on the same batches.
+    """Train every model of `modelsDict` (name -> TrainableModel) on the same batches. Names containing 'GCRNN' are gated
+    GCRNNs (archit(x, h0) on B x T x 1 x N); names without 'RNN' are graph neural networks such as 'Sel' (SelectionGNN), which
+    see every time step as a sample: x and y viewed as (B*T) x 1 x N, yHat = archit(x) (reference train_rnn.py:237-244,
+    263-267). Other recurrent models (the reference's non-graph RNNs) are not provided.
 
     xTrain / yTrain: nTrain x seqLen x N tensors (host or device); evaluate(yHat, y) is the dataset metric
     (batchTimeMSELoss for k-step prediction). With world > 1 each rank takes its shard of every batch and the
@@ -92,8 +117,12 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
         rng = np.random.RandomState(20231) if world > 1 else np.random
     nTrain = xTrain.shape[0]
     sizes, index = batch_partition(nTrain, batchSize)
-    dev = next(iter(modelsDict.values())).archit.stateGCRNN.weight_A.device
-    dt = dataType if dataType is not None else next(iter(modelsDict.values())).archit.stateGCRNN.weight_A.dtype
+    for key in modelsDict:
+        if not _is_gcrnn(key) and _is_rnn(key):
+            raise NotImplementedError('%s: only gated GCRNNs and graph neural networks (e.g. Sel) are provided' % key)
+    p0 = _first_parameter(next(iter(modelsDict.values())).archit)
+    dev = p0.device
+    dt = dataType if dataType is not None else p0.dtype
     syncs = {k: ((m.optim.sync if hasattr(m.optim, 'sync') else FlatGradAllReduce(m.archit.parameters())) if world > 1 else None)
              for k, m in modelsDict.items()}
     lossTrain = {k: [] for k in modelsDict}
@@ -113,12 +142,14 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
             xb = xTrain[idx].reshape(len(idx), seqLen, xTrain[0].numel() // seqLen).to(dev, dt)
             yb = yTrain[idx].reshape(len(idx), seqLen, yTrain[0].numel() // seqLen).to(dev, dt)
             for key, m in modelsDict.items():
-                assert 'GCRNN' in key or 'gcrnn' in key or 'GCRnn' in key        # reference dispatches on the name
                 xo = xb[:, :, m.order] if m.order is not None else xb
-                xo, yo = xo.unsqueeze(2), yb.unsqueeze(2)                         # B x T x 1 x N
+                if _is_gcrnn(key):
+                    xo, yo, fwd = xo.unsqueeze(2), yb.unsqueeze(2), None          # B x T x 1 x N
+                else:
+                    xo, yo, fwd = xo.reshape(-1, 1, xo.shape[2]), yb.reshape(-1, 1, yb.shape[2]), _gnn_forward     # (B*T) x 1 x N
                 torch.cuda.synchronize() if dev.type == 'cuda' else None
                 t0 = time.perf_counter()
-                loss, yHat = train_step(m.archit, m.loss, m.optim, xo, yo, stateFeat, syncs[key], share if world > 1 else None)
+                loss, yHat = train_step(m.archit, m.loss, m.optim, xo, yo, stateFeat, syncs[key], share if world > 1 else None, fwd)
                 torch.cuda.synchronize() if dev.type == 'cuda' else None
                 timeTrain[key].append(time.perf_counter() - t0)
                 lossTrain[key].append(float(loss))
@@ -130,8 +161,12 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
                 for key, m in modelsDict.items():
                     xv = (xv0[:, :, m.order] if m.order is not None else xv0).unsqueeze(2)      # reference train_rnn.py:349
                     with torch.no_grad():
-                        h0 = torch.zeros(xv.shape[0], stateFeat, xv.shape[3], dtype=dt, device=dev)
-                        score = float(evaluate(m.archit(xv, h0).to(yv.dtype), yv))
+                        if _is_gcrnn(key):
+                            h0 = torch.zeros(xv.shape[0], stateFeat, xv.shape[3], dtype=dt, device=dev)
+                            score = float(evaluate(m.archit(xv, h0).to(yv.dtype), yv))
+                        else:                                                     # reference train_rnn.py:354-356, 376-378
+                            yg = _gnn_forward(m.archit, xv.reshape(-1, 1, xv.shape[3]))
+                            score = float(evaluate(yg.to(yv.dtype), yv.reshape(-1, 1, yv.shape[3])))
                     evalValid[key].append(score)
                     if key not in best or score < best[key]:
                         best[key] = score

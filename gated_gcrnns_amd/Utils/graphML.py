@@ -7,6 +7,7 @@ names and shapes, `addGSO`, state_dict keys and AssertionError conventions.
     LSIGF(h, S, x, b=None)                                    reference graphML.py:47-140
     GraphFilter(G, F, K, E=1, bias=True)                      reference graphML.py:1086-1205
     GraphAttentional(G, F, K, E=1, nonlinearity, concatenate) reference graphML.py:1999-2128
+    NoPool(nInputNodes, nOutputNodes, nHops)                  reference graphML.py:906-944
     GGCRNNCell(G, F, Kin, Kst, sigma, time_gating, spatial_gating, E, bias)
                                                               reference graphML.py:2130-2427
 
@@ -100,6 +101,35 @@ class GraphFilter(nn.Module):
         return 'in_features=%d, out_features=%d, filter_taps=%d, edge_features=%d, bias=%s, %s' % (
             self.G, self.F, self.K, self.E, self.bias is not None,
             'GSO stored' if self.graph is not None else 'no GSO stored')
+
+
+class NoPool(nn.Module):
+    """Pooling layer that does no pooling (reference graphML.py:906-944): same signature as the pooling layers, identity forward."""
+
+    def __init__(self, nInputNodes, nOutputNodes, nHops):
+        super().__init__()
+        self.nInputNodes = nInputNodes
+        self.nOutputNodes = nOutputNodes
+        self.nHops = nHops
+        self.neighborhood = None
+
+    def addGSO(self, GSO):
+        pass
+
+    def forward(self, x):
+        assert x.shape[2] == self.nInputNodes
+        assert x.shape[2] >= self.nOutputNodes
+        return x
+
+    def extra_repr(self):
+        return 'in_dim=%d, out_dim=%d, number_hops = %d' % (self.nInputNodes, self.nOutputNodes, self.nHops) + 'no neighborhood needed'
+
+
+class MaxPoolLocal(nn.Module):
+    """Node-selecting pooling (reference graphML.py:946-1084) is not provided: constructing it raises."""
+
+    def __init__(self, nInputNodes, nOutputNodes, nHops):
+        raise NotImplementedError('MaxPoolLocal: pooling that selects nodes is not implemented; use NoPool with nSelectedNodes = [N, ...]')
 
 
 def _graph_attention_node_major(u, mixer, weight, graph, negative_slope=0.2):

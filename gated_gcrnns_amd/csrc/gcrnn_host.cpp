@@ -8,6 +8,7 @@
 #include <numeric>
 #include <vector>
 #include "../../include/gcrnn.h"
+#include "gcrnn_readout.h"
 
 extern "C" int gcrnn_version(void) { return 121; }  // 0.1.21 (round 5: hand-allocated-hop forward kernel, node-gated passes on the wide kernel, chunk pairs in the weight-gradient kernel)
 
@@ -638,4 +639,31 @@ extern "C" int gcrnn_ell_assign_rows_z(const int32_t* rowptr, const int32_t* col
     next_row[a] += 4;
   }
   return GCRNN_OK;
+}
+
+// ---- graph-filter layer (gcrnn_readout.hip): envelope and slot count, host logic only ---------------------------------------
+static int64_t gfl_lds(int dtype, int64_t N, int64_t nnz, int64_t F_in, int64_t F_out, int64_t K, int uniform) {
+  const int64_t acc = dtype == GCRNN_F64 ? 8 : 4;
+  const int64_t f = gfl_layout(N, nnz, F_in, F_out, K, acc, 0, uniform).total, b = gfl_layout(N, nnz, F_in, F_out, K, acc, 1, uniform).total;
+  return f > b ? f : b;
+}
+
+extern "C" int gcrnn_graph_filter_layer_supported(int dtype, int64_t N, int64_t nnz, int64_t E, int64_t F_in, int64_t F_out, int64_t K,
+                                                  int uniform) {
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64 && dtype != GCRNN_BF16) return 0;
+  if (E != 1 || N <= 0 || N > GFL_MAX_N || nnz < 0 || nnz > N * N || F_in <= 0 || F_out <= 0 || K <= 0) return 0;
+  if (F_in > 4096 || F_out > 4096 || K > 64) return 0;
+  return gfl_lds(dtype, N, nnz, F_in, F_out, K, uniform) <= GFL_LDS_BYTES ? 1 : 0;
+}
+
+// one workgroup per slot: as many as fit on the chip at once (LDS-bound, at most 4 per CU), never more than there are items
+extern "C" int64_t gcrnn_graph_filter_layer_wgrad_slots(int dtype, int64_t items, int64_t N, int64_t nnz, int64_t F_in, int64_t F_out,
+                                                        int64_t K, int uniform) {
+  if (items <= 0) return 0;
+  const int64_t lds = gfl_lds(dtype, N > 0 ? N : 1, nnz > 0 ? nnz : 0, F_in > 0 ? F_in : 1, F_out > 0 ? F_out : 1, K > 0 ? K : 1, uniform);
+  int64_t per_cu = lds > 0 ? GFL_LDS_BYTES / lds : 4;
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 4) per_cu = 4;
+  const int64_t slots = GFL_CUS * per_cu;
+  return items < slots ? items : slots;
 }

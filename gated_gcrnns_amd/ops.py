@@ -2879,6 +2879,97 @@ def node_linear(h, weight, bias=None):
     return _NodeLinear.apply(h, weight, bias)
 
 
+# ------------------------------------------------------------------------------------------ graph-filter layer (GNN output heads)
+_GFL_ACTS = {None: 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3}
+
+
+def _gfl_uniform(csr):
+    """The one weight every edge of `csr` carries (0.0: weights differ). Read once per CSR and kept on it."""
+    u = getattr(csr, '_gfl_uniform', None)
+    if u is None:
+        v = csr.val(torch.float64)
+        u = float(v[0]) if csr.nnz > 0 and bool((v == v[0]).all()) else 0.0
+        csr._gfl_uniform = u
+    return u
+
+
+def graph_filter_layer_supported(x_dtype, w_dtype, graph, F_in, F_out, K):
+    """True when gcrnn_graph_filter_layer_{forward,backward} evaluate this layer: bf16 x with fp32 parameters, or fp32 / fp64
+    throughout; E = 1, N <= 1024 and an LDS image that fits one CU."""
+    if not ((x_dtype == torch.bfloat16 and w_dtype == torch.float32) or (x_dtype == w_dtype and x_dtype in (torch.float32, torch.float64))):
+        return False
+    if graph.E != 1:
+        return False
+    csr = graph.fwd[0]
+    uni = int(_gfl_uniform(csr) != 0.0 and _gfl_uniform(graph.adj[0]) != 0.0)
+    return bool(lib.gcrnn_graph_filter_layer_supported(dtype_code(x_dtype), graph.N, csr.nnz, graph.E, int(F_in), int(F_out), int(K), uni))
+
+
+class _GraphFilterLayer(torch.autograd.Function):
+    """act(LSIGF(w, S, x, b)) of one GraphFilter (graphML.py:1086-1205) in one launch per pass (gcrnn_readout.hip).
+    x [items][F_in][N] -> y [items][F_out][N] in the parameters' dtype; the parameters are read as they are on every call."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, graph, act):
+        require_device(x, w, b)
+        xc, wc = x.contiguous(), w.contiguous()
+        bc = b.contiguous() if b is not None else None
+        items, Fin, N = xc.shape
+        Fout, E, K, _ = wc.shape
+        csr = graph.fwd[0]
+        uw = _gfl_uniform(csr)
+        y = torch.empty((items, Fout, N), dtype=wc.dtype, device=xc.device)
+        check(lib.gcrnn_graph_filter_layer_forward(dtype_code(xc.dtype), _p(xc), _p(wc), _p(bc), _p(y), _p(csr.rowptr), _p(csr.col),
+                                                   None if uw else _p(csr.val(wc.dtype)), uw, items, N, csr.nnz, E, Fin, Fout, K,
+                                                   _GFL_ACTS[act], _stream()), 'graph_filter_layer_forward')
+        ctx.save_for_backward(xc, wc, y)
+        ctx.graph, ctx.act, ctx.has_bias = graph, act, b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        items, Fin, N = x.shape
+        Fout, E, K, _ = w.shape
+        adj = ctx.graph.adj[0]
+        uw = _gfl_uniform(adj)
+        code = dtype_code(x.dtype)
+        slots = int(lib.gcrnn_graph_filter_layer_wgrad_slots(code, items, N, adj.nnz, Fin, Fout, K, int(uw != 0.0)))
+        dwp = torch.empty((slots, Fout * K * Fin), dtype=w.dtype, device=x.device)
+        dbp = torch.empty((slots, Fout), dtype=w.dtype, device=x.device) if ctx.has_bias else None
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dyc = dy.contiguous().to(w.dtype)
+        check(lib.gcrnn_graph_filter_layer_backward(code, _p(x), _p(w), _p(y), _p(dyc), _p(dx), _p(dwp), _p(dbp), slots, _p(adj.rowptr),
+                                                    _p(adj.col), None if uw else _p(adj.val(w.dtype)), uw, items, N, adj.nnz, E, Fin,
+                                                    Fout, K, _GFL_ACTS[ctx.act], _stream()), 'graph_filter_layer_backward')
+        dw = dwp.sum(dim=0).reshape(w.shape)
+        db = dbp.sum(dim=0).reshape(Fout, 1) if ctx.has_bias else None
+        return dx, dw, db, None, None
+
+
+def _graph_filter_layer_composed(x, weight, bias, graph, act):
+    """The composed path outside the kernel's envelope: GraphFilter.forward (LSIGF on the node-major filter ops) + the torch
+    activation, in the parameters' dtype."""
+    from .Utils import graphML as gml
+    y = gml.LSIGF(weight, graph, x.to(weight.dtype), bias)
+    return {None: lambda t: t, 'relu': torch.relu, 'tanh': torch.tanh, 'sigmoid': torch.sigmoid}[act](y)
+
+
+def graph_filter_layer(x, weight, bias, graph, act=None):
+    """y = act( sum_k w[:, 0, k, :] (x S^k) + b ) for x [items][F_in][N], weight F_out x E x K x F_in, bias F_out x 1 (or None),
+    act in (None, 'relu', 'tanh', 'sigmoid'). One HIP launch per pass where graph_filter_layer_supported says so, else the composed
+    filter path."""
+    assert act in _GFL_ACTS, act
+    assert x.dim() == 3 and x.shape[1] == weight.shape[3] and x.shape[2] == graph.N, (tuple(x.shape), tuple(weight.shape), graph.N)
+    Fout, E, K, Fin = weight.shape
+    if graph.device != x.device:
+        graph = graph.to(x.device)
+    if x.is_cuda and E == graph.E and graph_filter_layer_supported(x.dtype, weight.dtype, graph, Fin, Fout, K) and \
+            (bias is None or bias.dtype == weight.dtype):
+        return _GraphFilterLayer.apply(x, weight, bias, graph, act)
+    return _graph_filter_layer_composed(x, weight, bias, graph, act)
+
+
 # ------------------------------------------------------------------------------------------ loss
 class _L1Loss(torch.autograd.Function):
     """mean |x - y| with the gradient produced in the same pass (reference batchTimeL1Loss, miscTools.py:112-119)."""

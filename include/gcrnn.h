@@ -711,6 +711,32 @@ int gcrnn_node_linear_bf16_forward(int wdtype, const void* h, const void* w, con
 int gcrnn_node_linear_bf16_backward(int wdtype, const void* h, const void* w, const void* dy, void* dh, float* pw, float* pb,
                                     int64_t R, int64_t N, int64_t F, int64_t O, void* stream);
 
+/* ==== graph-filter layer: the GNN output heads ====================================================================
+ * One GraphFilter (graphML.py:1086-1205) with bias and activation, the layer of SelectionGNN (architectures.py:10-177) and of
+ * the Selection-GNN output network C(S) of the gated GCRNNs, on the user layout, one launch per pass:
+ *   y[i][o][n] = act( sum_k sum_f w[o][0][k][f] (x_i S^k)[f][n] + b[o] ),  (x S)[f][n] = sum_m x[f][m] S[m][n].
+ * x [items][F_in][N] of `dtype` (GCRNN_BF16 with fp32 parameters and accumulation, GCRNN_F32, or GCRNN_F64 throughout);
+ * w [F_out][1][K][F_in], b [F_out] (or NULL), y / dy [items][F_out][N] in the accumulation type (fp32; fp64 for GCRNN_F64);
+ * act: 0 identity, 1 ReLU, 2 tanh, 3 sigmoid. forward: rowptr/col/val = CSR(S^T) (GraphOperator.fwd[0]); backward: CSR(S)
+ * (GraphOperator.adj[0]); val in the accumulation type, or NULL with uniform_w != 0 (every edge weighs uniform_w).
+ * supported: E == 1, N <= 1024 and the LDS image (weights, CSR rows, K running signals of min(F_in, F_out) channels forward,
+ * K of F_out backward) fits one CU; the entry points return GCRNN_ERR_UNSUPPORTED otherwise, before any launch.
+ * backward: g = dy * act'(y) from the stored y; dx [items][F_in][N] in x's dtype (or NULL); dw_parts [slots][F_out][K][F_in] and
+ * db_parts [slots][F_out] (or NULL) per-workgroup partial sums in the accumulation type, every slot written, added by the caller
+ * in a fixed order (deterministic). slots must equal gcrnn_graph_filter_layer_wgrad_slots(...) of the same problem, else
+ * GCRNN_ERR_WORKSPACE. */
+int gcrnn_graph_filter_layer_supported(int dtype, int64_t N, int64_t nnz, int64_t E, int64_t F_in, int64_t F_out, int64_t K,
+                                       int uniform);
+int64_t gcrnn_graph_filter_layer_wgrad_slots(int dtype, int64_t items, int64_t N, int64_t nnz, int64_t F_in, int64_t F_out,
+                                             int64_t K, int uniform);
+int gcrnn_graph_filter_layer_forward(int dtype, const void* x, const void* w, const void* b, void* y, const int32_t* rowptr,
+                                     const int32_t* col, const void* val, double uniform_w, int64_t items, int64_t N, int64_t nnz,
+                                     int64_t E, int64_t F_in, int64_t F_out, int64_t K, int act, void* stream);
+int gcrnn_graph_filter_layer_backward(int dtype, const void* x, const void* w, const void* y, const void* dy, void* dx,
+                                      void* dw_parts, void* db_parts, int64_t slots, const int32_t* rowptr, const int32_t* col,
+                                      const void* val, double uniform_w, int64_t items, int64_t N, int64_t nnz, int64_t E,
+                                      int64_t F_in, int64_t F_out, int64_t K, int act, void* stream);
+
 /* ==== training-loop loss ==========================================================================================
  * batchTimeL1Loss (Utils/miscTools.py:112-119 = nn.L1Loss: mean |x - y| over every entry) and its gradient in one pass.
  * x, y, grad: n contiguous elements of `dtype` (F32 / F64 / BF16), 16-byte aligned; grad (may be NULL) =
