@@ -12,12 +12,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 import gated_gcrnns_amd.Modules.architectures as archit
-from shape_sweep import random_graph
+from shape_sweep import pin_cell_to_torch_reference, random_graph
 
 
 def main(quick=False):
     dev = torch.device('cuda:0')
     fails, n = [], 0
+    pinned = set()
     gatings = ((False, None), (True, None), (False, 'node'), (True, 'node'), (False, 'edge'))
     heads = (('reg', 'multipMlp', [1]), ('reg', 'oneMlp', [40]), ('reg', 'multipMlp', [8, 1]), ('cls', None, [5]))
     for N in ((1000,) if quick else (80, 1000)):
@@ -54,6 +55,15 @@ def main(quick=False):
                     return y.detach().double(), {k: q.grad.detach().double().clone() for k, q in c.named_parameters() if q.grad is not None}
                 y1, g1 = run(m, X, h0)
                 yr, gr = run(ref, X.double(), h0.double())
+                if (N, tg, sg, train) not in pinned:               # the fp64 state cell (the truth's recurrence), once per gating and mode
+                    pinned.add((N, tg, sg, train))
+                    X2, h02 = X[:2].double(), h0[:2].double()
+                    if train:
+                        H2 = ref.stateGCRNN(X2, h02)
+                    else:
+                        with torch.no_grad():
+                            H2 = ref.stateGCRNN(X2, h02)
+                    pin_cell_to_torch_reference(ref.stateGCRNN, S, X2, h02, H2.detach())
                 assert y1.shape == yr.shape, 'shapes %s vs %s' % (tuple(y1.shape), tuple(yr.shape))
                 assert torch.isfinite(y1).all(), 'non-finite output'
                 ysc = max(float(yr.abs().max()), 1e-3)
