@@ -13,7 +13,8 @@ stations) of the source. Same tensor shapes and model as the driver: x is B x T 
 
 --models picks the driver's other models (epicenterEstimation.py:150-153, 180-196, 258-280): 'Sel' = SelectionGNN([T, 21], [taps],
 ReLU, NoPool, MLP [11]) on the window's T samples as node features, 'GCRNNGNN' / 'TimeGCRNNGNN' = the gated GCRNN with a
-Selection-GNN head [F, 1], K = taps, MLP [11], final ReLU. Default: the MLP-head GCRNN ('TimeGCRNNMLP' with --time-gating).
+Selection-GNN head [F, 1], K = taps, MLP [11], final ReLU, 'RNNMLP' = the driver's RNN baseline RNNforClassification(1,
+--rnn-features, 'tanh', [11], ReLU) on the flattened window (epicenterEstimation.py:151, 172, 284-300). Default: the MLP-head GCRNN ('TimeGCRNNMLP' with --time-gating).
 
 Measured on one MI355X (fp64, batch 100): T=200 3.6 ms per optimiser step, 84 % test accuracy after 600 steps (chance 9 %);
 T=50 1.1 ms per step, 99.8 %. The time-gated variant trains at 2.0 ms per step (T=50) but needs the reference's
@@ -51,7 +52,7 @@ def synthetic_waves(S, n, T, regions, rng):
     return x, regions[src]
 
 
-MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN')
+MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN', 'RNNMLP')
 
 
 def main(argv=None):
@@ -63,6 +64,7 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=600)
     ap.add_argument('--lr', type=float, default=5e-3, help='the reference driver uses 1e-3 over many epochs')
     ap.add_argument('--time-gating', action='store_true')
+    ap.add_argument('--rnn-features', type=int, default=21, help="RNNMLP's state features (the driver's rnnStateFeat)")
     ap.add_argument('--dtype', default='f64', choices=['f32', 'f64'])
     ap.add_argument('--models', default=None, help='comma-separated, of ' + ','.join(MODELS) + ' (default: one MLP-head GCRNN)')
     args = ap.parse_args(argv)
@@ -90,6 +92,12 @@ def main(argv=None):
         if gnn:
             model = archit.SelectionGNN([args.seq, 21], [args.taps], True, torch.nn.ReLU, [N], gml.NoPool, [1], [11], S).to(dev)
             fwd = lambda a, x: a(x.squeeze(2))                           # the T samples of a window are the node features
+        elif name == 'RNNMLP':
+            model = archit.RNNforClassification(1, args.rnn_features, 'tanh', [11], torch.nn.ReLU, S, True).to(dev)
+
+            def fwd(a, x):
+                h0 = torch.zeros(x.shape[0], args.rnn_features, dtype=x.dtype, device=x.device)
+                return a(x, h0, h0)                                      # c0 = h0 (reference train_rnn.py:248-250)
         else:
             tg = name.startswith('Time')
             head = dict(finalNonlinearity=torch.nn.ReLU, dimNodeSignals=[args.features, 1], nFilterTaps=[args.taps], nSelectedNodes=[N],
@@ -110,6 +118,9 @@ def main(argv=None):
         with torch.no_grad():
             if gnn:
                 logits = model(xe.squeeze(2))
+            elif name == 'RNNMLP':
+                h0 = torch.zeros(xe.shape[0], args.rnn_features, dtype=dt, device=dev)
+                logits = model(xe, h0, h0)
             else:
                 logits = model(xe, torch.zeros(xe.shape[0], args.features, N, dtype=dt, device=dev))
             acc = float((logits.argmax(dim=1).cpu() == torch.tensor(yte)).double().mean())

@@ -10,7 +10,8 @@ bf16 batches to fp32 master weights: all four variants (un-gated, time-, node- a
 (N <= 1024, F in {32, 64}; other shapes: composed path in fp32). --sparse draws the BASELINE configs[1] graph (mean degree ~10).
 --models also accepts the driver's GNN models: 'Sel' (SelectionGNN([1, 8, 1], [10, 10], ReLU, NoPool), every time step a sample,
 kStepPredGRNNs.py:197) and 'GCRNNGNN' / 'TimeGCRNNGNN' (a Selection-GNN head [F, 1], K = taps, final ReLU; the driver's [5, 1]
-with F = 20 fails the reference's own shape assert).
+with F = 20 fails the reference's own shape assert), and 'RNNMLP' (the driver's RNN baseline: RNNforRegression(1, --rnn-features,
+'tanh', [1], ReLU), kStepPredGRNNs.py:285-301).
 """
 import argparse
 import os
@@ -28,7 +29,7 @@ from gated_gcrnns_amd.Utils import dataTools, miscTools
 from gated_gcrnns_amd.optim import FlatAdam
 
 
-MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'NodeGCRNNMLP', 'EdgeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN')
+MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'NodeGCRNNMLP', 'EdgeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN', 'RNNMLP')
 
 
 def main(argv=None):
@@ -45,6 +46,7 @@ def main(argv=None):
     ap.add_argument('--sparse', action='store_true', help='SBM with p_in 0.04 / p_out 0.0025 (BASELINE configs[1]) instead of 0.8 / 0.2')
     ap.add_argument('--models', default='GCRNNMLP,TimeGCRNNMLP,NodeGCRNNMLP,EdgeGCRNNMLP',
                     help='comma-separated, of ' + ','.join(MODELS))
+    ap.add_argument('--rnn-features', type=int, default=1, help="RNNMLP's state features (the driver's rnnStateFeat)")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--optim', default='flat', choices=['flat', 'torch'], help='flat: optim.FlatAdam (one kernel over the flat '
                     'parameter / gradient buffers); torch: torch.optim.Adam as in the reference driver')
@@ -82,6 +84,8 @@ def main(argv=None):
             m = archit.GatedGCRNNforRegression(1, args.features, args.taps, args.taps, torch.tanh, torch.nn.ReLU, [], S, True,
                                                name == 'TimeGCRNNGNN', None, 'oneMlp', torch.nn.ReLU, [args.features, 1], [args.taps],
                                                [args.nodes], gml.NoPool, [1])
+        elif name == 'RNNMLP':
+            m = archit.RNNforRegression(1, args.rnn_features, 'tanh', [1], torch.nn.ReLU, S, True)
         else:
             continue
         m = m.to(dev)
@@ -91,7 +95,7 @@ def main(argv=None):
     xT, yT = data.getSamples('train')
     xV, yV = data.getSamples('valid')
     out = MultipleModels(models, xT, yT, xV, yV, args.epochs, args.batch, data.seqLen, args.features,
-                         data.evaluate, validationInterval=5, rng=rng, doPrint=False, dataType=data_dt)
+                         data.evaluate, validationInterval=5, rng=rng, doPrint=False, dataType=data_dt, rnnStateFeat=args.rnn_features)
     xE, yE = data.getSamples('test')
     xE = xE.view(xE.shape[0], data.seqLen, -1).to(dev, data_dt).unsqueeze(2)
     yE = yE.view(yE.shape[0], data.seqLen, -1).to(dev, data_dt).unsqueeze(2)
@@ -102,6 +106,9 @@ def main(argv=None):
             if name == 'Sel':                                             # every time step a sample (reference train_rnn.py:243)
                 yS = tm.archit(xE.reshape(-1, 1, args.nodes).to(dt)).unsqueeze(1)
                 score = float(data.evaluate(yS.to(yE.dtype), yE.reshape(-1, 1, args.nodes)))
+            elif name == 'RNNMLP':                                        # reference train_rnn.py:246-251
+                h0 = torch.zeros(xE.shape[0], args.rnn_features, device=dev, dtype=data_dt)
+                score = float(data.evaluate(tm.archit(xE, h0, h0).to(yE.dtype), yE))
             else:
                 h0 = torch.zeros(xE.shape[0], args.features, args.nodes, device=dev, dtype=data_dt)
                 score = float(data.evaluate(tm.archit(xE, h0).to(yE.dtype), yE))

@@ -5,7 +5,8 @@ Same positional constructor signatures, attribute names and state_dict keys
 (`stateGCRNN.*`, `outputNN.<i>.*`). Output heads: the MLPs (the drivers' 'multipMlp' /
 'oneMlp') and the Selection GNN (reference architectures.py:10-177, also stand-alone as
 `SelectionGNN`) without node-selecting pooling; every graph-filter layer of it runs as one
-HIP launch per pass (ops.graph_filter_layer). Aggregation-GNN heads are not provided.
+HIP launch per pass (ops.graph_filter_layer). Aggregation-GNN heads are not provided. The drivers' plain-RNN
+baselines (reference :1861-2149) are `RNNforRegression` / `RNNforClassification` on ops.rnn_sequence.
 """
 import numpy as np
 import torch
@@ -232,3 +233,105 @@ class GatedGCRNNforClassification(_GatedGCRNNBase):
         if self.gnn_head:
             return self.outputNN(h)                                  # reference :1848-1849
         return self.outputNN(_to_param_dtype(h, self.outputNN).reshape(-1, self.F_h * self.N))
+
+
+class _RNNParameters(nn.Module):
+    """The parameters of the reference's torch.nn.RNN(D, F_h, num_layers=1, nonlinearity, bias, batch_first=True), under the same
+    names (`weight_ih_l0`, `weight_hh_l0`, `bias_ih_l0`, `bias_hh_l0`) and drawn in the same order with the same
+    uniform(-1/sqrt(F_h), 1/sqrt(F_h)), so that seeded models start from the reference's values. The recurrence itself is
+    ops.rnn_sequence (gcrnn_rnn.hip); torch.nn.RNN is not instantiated."""
+
+    def __init__(self, input_size, hidden_size, nonlinearity='tanh', bias=True):
+        super().__init__()
+        if nonlinearity not in ('tanh', 'relu'):                   # torch.nn.RNN's check, before any parameter exists
+            raise ValueError("Unknown nonlinearity '%s'. Select from 'tanh' or 'relu'." % (nonlinearity,))
+        if not isinstance(hidden_size, int):
+            raise TypeError('hidden_size should be of type int, got: %s' % type(hidden_size).__name__)
+        if hidden_size <= 0:
+            raise ValueError('hidden_size must be greater than zero')
+        self.input_size, self.hidden_size, self.nonlinearity, self.bias = input_size, hidden_size, nonlinearity, bias
+        self.weight_ih_l0 = nn.Parameter(torch.empty(hidden_size, input_size))
+        self.weight_hh_l0 = nn.Parameter(torch.empty(hidden_size, hidden_size))
+        if bias:
+            self.bias_ih_l0 = nn.Parameter(torch.empty(hidden_size))
+            self.bias_hh_l0 = nn.Parameter(torch.empty(hidden_size))
+        else:
+            self.bias_ih_l0 = self.bias_hh_l0 = None
+        stdv = 1.0 / np.sqrt(hidden_size)
+        for p in self.parameters():                                  # torch.nn.RNN.reset_parameters
+            nn.init.uniform_(p, -stdv, stdv)
+
+    def forward(self, x, h0):
+        """x: B x T x D, h0: B x F_h -> H: B x T x F_h."""
+        return ops.rnn_sequence(x, h0, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0, self.nonlinearity)
+
+
+class _RNNBase(nn.Module):
+    def _init_rnn(self, inFeatures, stateFeatures, stateNonlinearity, dimLayersMLP, outputNonlinearity, GSO, bias,
+                  finalNonlinearity, outMult):
+        S = _as_gso_tensor(GSO)
+        self.F_i = inFeatures
+        self.F_h = stateFeatures
+        self.E = int(S.shape[0])
+        self.N = int(S.shape[1])
+        self.bias = bias
+        self.register_buffer('S', S, persistent=False)            # moved by .to(); not in state_dict (as the reference)
+        self.sigma1 = stateNonlinearity
+        self.RNN = _RNNParameters(self.N * self.F_i, self.F_h, nonlinearity=self.sigma1, bias=self.bias)
+        self.dimLayersMLP = dimLayersMLP
+        self.sigma2 = outputNonlinearity
+        self.sigma3 = finalNonlinearity
+        fc = []                                                   # reference :1952-1968 / :2102-2118; the last layer's width * outMult
+        if len(dimLayersMLP) > 0:
+            if len(dimLayersMLP) != 1:
+                fc.append(nn.Linear(self.F_h, dimLayersMLP[0], bias=self.bias))
+                for l in range(len(dimLayersMLP) - 1):
+                    fc.append(self.sigma2())
+                    last = l == len(dimLayersMLP) - 2
+                    fc.append(nn.Linear(dimLayersMLP[l], dimLayersMLP[l + 1] * (outMult if last else 1), bias=self.bias))
+            else:
+                fc.append(nn.Linear(self.F_h, dimLayersMLP[0] * outMult, bias=self.bias))
+        if self.sigma3 is not None:
+            fc.append(self.sigma3())
+        self.outputNN = nn.Sequential(*fc)
+
+    def _states(self, x, h0):
+        batchSize, seqLength = x.shape[0], x.shape[1]
+        return self.RNN(x.reshape(batchSize, seqLength, -1), h0.reshape(batchSize, -1))      # B x T x F_h
+
+
+class RNNforRegression(_RNNBase):
+    """The drivers' RNN baseline for regression (reference architectures.py:1861-2004): a one-layer RNN on the flattened graph signal
+    (input index f*N + n) and an MLP on every state. Same signature, state_dict keys (`RNN.weight_ih_l0`, ..., `outputNN.<i>.*`) and
+    seeded initialisation. The recurrence runs on the HIP kernels of ops.rnn_sequence; the MLP is nn.Linear.
+
+    forward(x: B x T x F_i x N, h0: B x F_h, c0: ignored) -> B x T x out x N.
+    """
+
+    def __init__(self, inFeatures, stateFeatures, stateNonlinearity, dimLayersMLP, outputNonlinearity, GSO, bias,
+                 finalNonlinearity=None):
+        super().__init__()
+        self._init_rnn(inFeatures, stateFeatures, stateNonlinearity, dimLayersMLP, outputNonlinearity, GSO, bias, finalNonlinearity,
+                       _as_gso_tensor(GSO).shape[1])
+
+    def forward(self, x, h0, c0):
+        batchSize, seqLength = x.shape[0], x.shape[1]
+        H = self._states(x, h0)
+        flatY = self.outputNN(_to_param_dtype(H.reshape(batchSize * seqLength, self.F_h), self.outputNN))
+        return flatY.view(batchSize, seqLength, -1, self.N)
+
+
+class RNNforClassification(_RNNBase):
+    """The drivers' RNN baseline for classification (reference architectures.py:2006-2149): the MLP on the last state only.
+
+    forward(x: B x T x F_i x N, h0: B x F_h, c0: ignored) -> B x dimLayersMLP[-1].
+    """
+
+    def __init__(self, inFeatures, stateFeatures, stateNonlinearity, dimLayersMLP, outputNonlinearity, GSO, bias,
+                 finalNonlinearity=None):
+        super().__init__()
+        self._init_rnn(inFeatures, stateFeatures, stateNonlinearity, dimLayersMLP, outputNonlinearity, GSO, bias, finalNonlinearity, 1)
+
+    def forward(self, x, h0, c0):
+        H = self._states(x, h0)
+        return self.outputNN(_to_param_dtype(H.select(1, -1), self.outputNN))

@@ -93,16 +93,25 @@ def _gnn_forward(archit, x):
     return archit(x).unsqueeze(1)
 
 
+def _rnn_forward(F):
+    """The reference's plain-RNN branch (train_rnn.py:246-251): h0 = zeros(B, rnnStateFeat), c0 = h0, archit(x, h0, c0)."""
+    def fwd(archit, x):
+        h0 = torch.zeros(x.shape[0], F, dtype=x.dtype, device=x.device)
+        return archit(x, h0, h0)
+    return fwd
+
+
 def _first_parameter(archit):
     return archit.stateGCRNN.weight_A if hasattr(archit, 'stateGCRNN') else next(archit.parameters())
 
 
 def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSize, seqLen, stateFeat,
-                   evaluate, validationInterval=5, rank=0, world=1, doPrint=False, rng=None, dataType=None):
+                   evaluate, validationInterval=5, rank=0, world=1, doPrint=False, rng=None, dataType=None, rnnStateFeat=None):
     """Train every model of `modelsDict` (name -> TrainableModel) on the same batches. Names containing 'GCRNN' are gated
-    GCRNNs (archit(x, h0) on B x T x 1 x N); names without 'RNN' are graph neural networks such as 'Sel' (SelectionGNN), which
-    see every time step as a sample: x and y viewed as (B*T) x 1 x N, yHat = archit(x) (reference train_rnn.py:237-244,
-    263-267). Other recurrent models (the reference's non-graph RNNs) are not provided.
+    GCRNNs (archit(x, h0) on B x T x 1 x N); other names containing 'RNN' are the plain RNN baselines such as 'RNNMLP'
+    (RNNforRegression: archit(x, h0, c0) on B x T x 1 x N with h0 = c0 = zeros(B, rnnStateFeat); rnnStateFeat=None takes the
+    model's F_h); names without 'RNN' are graph neural networks such as 'Sel' (SelectionGNN), which see every time step as a
+    sample: x and y viewed as (B*T) x 1 x N, yHat = archit(x) (reference train_rnn.py:237-267).
 
     xTrain / yTrain: nTrain x seqLen x N tensors (host or device); evaluate(yHat, y) is the dataset metric
     (batchTimeMSELoss for k-step prediction). With world > 1 each rank takes its shard of every batch and the
@@ -117,9 +126,8 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
         rng = np.random.RandomState(20231) if world > 1 else np.random
     nTrain = xTrain.shape[0]
     sizes, index = batch_partition(nTrain, batchSize)
-    for key in modelsDict:
-        if not _is_gcrnn(key) and _is_rnn(key):
-            raise NotImplementedError('%s: only gated GCRNNs and graph neural networks (e.g. Sel) are provided' % key)
+    rnnFwd = {k: _rnn_forward(rnnStateFeat if rnnStateFeat is not None else m.archit.F_h)
+              for k, m in modelsDict.items() if not _is_gcrnn(k) and _is_rnn(k)}
     p0 = _first_parameter(next(iter(modelsDict.values())).archit)
     dev = p0.device
     dt = dataType if dataType is not None else p0.dtype
@@ -143,8 +151,8 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
             yb = yTrain[idx].reshape(len(idx), seqLen, yTrain[0].numel() // seqLen).to(dev, dt)
             for key, m in modelsDict.items():
                 xo = xb[:, :, m.order] if m.order is not None else xb
-                if _is_gcrnn(key):
-                    xo, yo, fwd = xo.unsqueeze(2), yb.unsqueeze(2), None          # B x T x 1 x N
+                if _is_gcrnn(key) or key in rnnFwd:
+                    xo, yo, fwd = xo.unsqueeze(2), yb.unsqueeze(2), rnnFwd.get(key)   # B x T x 1 x N
                 else:
                     xo, yo, fwd = xo.reshape(-1, 1, xo.shape[2]), yb.reshape(-1, 1, yb.shape[2]), _gnn_forward     # (B*T) x 1 x N
                 torch.cuda.synchronize() if dev.type == 'cuda' else None
@@ -164,6 +172,8 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
                         if _is_gcrnn(key):
                             h0 = torch.zeros(xv.shape[0], stateFeat, xv.shape[3], dtype=dt, device=dev)
                             score = float(evaluate(m.archit(xv, h0).to(yv.dtype), yv))
+                        elif key in rnnFwd:                                # reference train_rnn.py:357-362
+                            score = float(evaluate(rnnFwd[key](m.archit, xv).to(yv.dtype), yv))
                         else:                                                     # reference train_rnn.py:354-356, 376-378
                             yg = _gnn_forward(m.archit, xv.reshape(-1, 1, xv.shape[3]))
                             score = float(evaluate(yg.to(yv.dtype), yv.reshape(-1, 1, yv.shape[3])))

@@ -167,6 +167,10 @@ def _bind(lib):
         'gcrnn_graph_filter_layer_forward': (C.c_int, [C.c_int] + [_c_p] * 7 + [C.c_double] + [_c_i64] * 7 + [C.c_int, _c_p]),
         'gcrnn_graph_filter_layer_backward': (C.c_int, [C.c_int] + [_c_p] * 7 + [_c_i64] + [_c_p] * 3 + [C.c_double] + [_c_i64] * 7
                                               + [C.c_int, _c_p]),
+        'gcrnn_rnn_supported': (C.c_int, [C.c_int] + [_c_i64] * 4),
+        'gcrnn_rnn_wgrad_slots': (_c_i64, [C.c_int] + [_c_i64] * 4),
+        'gcrnn_rnn_forward': (C.c_int, [C.c_int] + [_c_p] * 7 + [_c_i64] * 4 + [C.c_int, _c_p]),
+        'gcrnn_rnn_backward': (C.c_int, [C.c_int] + [_c_p] * 10 + [_c_i64] * 5 + [C.c_int, _c_p]),
         'gcrnn_l1_loss_blocks': (_c_i64, [_c_i64]),
         'gcrnn_l1_loss': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_i64, C.c_double, _c_p]),
         'gcrnn_scale_unless_one': (C.c_int, [C.c_int, _c_p, _c_p, _c_i64, _c_p]),

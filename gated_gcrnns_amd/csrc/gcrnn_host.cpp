@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../include/gcrnn.h"
 #include "gcrnn_readout.h"
+#include "gcrnn_rnn.h"
 
 extern "C" int gcrnn_version(void) { return 121; }  // 0.1.21 (round 5: hand-allocated-hop forward kernel, node-gated passes on the wide kernel, chunk pairs in the weight-gradient kernel)
 
@@ -666,4 +667,15 @@ extern "C" int64_t gcrnn_graph_filter_layer_wgrad_slots(int dtype, int64_t items
   if (per_cu > 4) per_cu = 4;
   const int64_t slots = GFL_CUS * per_cu;
   return items < slots ? items : slots;
+}
+
+// ---- plain RNN (gcrnn_rnn.hip): envelope and slot count from rnn_layout, host logic only ------------------------------------------
+extern "C" int gcrnn_rnn_supported(int dtype, int64_t B, int64_t T, int64_t D, int64_t F_h) {
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return 0;
+  return rnn_layout(B, T, D, F_h).ok;
+}
+
+extern "C" int64_t gcrnn_rnn_wgrad_slots(int dtype, int64_t B, int64_t T, int64_t D, int64_t F_h) {
+  if (!gcrnn_rnn_supported(dtype, B, T, D, F_h)) return 0;
+  return rnn_layout(B, T, D, F_h).slots;
 }

@@ -2970,6 +2970,86 @@ def graph_filter_layer(x, weight, bias, graph, act=None):
     return _graph_filter_layer_composed(x, weight, bias, graph, act)
 
 
+# ------------------------------------------------------------------------------------------ plain RNN (the drivers' RNN baselines)
+_RNN_ACTS = {'tanh': 0, 'relu': 1}
+
+
+def rnn_supported(dtype, B, T, D, F_h):
+    """True when gcrnn_rnn_{forward,backward} evaluate this recurrence: fp32 or fp64, 1 <= F_h <= 64, D <= 65536 (gcrnn_rnn.h)."""
+    if dtype not in (torch.float32, torch.float64):
+        return False
+    return bool(lib.gcrnn_rnn_supported(dtype_code(dtype), int(B), int(T), int(D), int(F_h)))
+
+
+class _RnnSequence(torch.autograd.Function):
+    """H = torch.nn.RNN(D, F_h, 1, nonlinearity, bias, batch_first=True)(x, h0)[0] on the HIP kernels (gcrnn_rnn.hip): two launches
+    forward, at most three backward plus the sum of the weight-gradient slots, whatever T is."""
+
+    @staticmethod
+    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, nonlinearity):
+        require_device(x, h0, w_ih, w_hh, b_ih, b_hh)
+        xc, hc, wi, wh = x.contiguous(), h0.contiguous(), w_ih.contiguous(), w_hh.contiguous()
+        bi = b_ih.contiguous() if b_ih is not None else None
+        bh = b_hh.contiguous() if b_hh is not None else None
+        B, T, D = xc.shape
+        Fh = wh.shape[0]
+        H = torch.empty((B, T, Fh), dtype=xc.dtype, device=xc.device)
+        check(lib.gcrnn_rnn_forward(dtype_code(xc.dtype), _p(xc), _p(hc), _p(wi), _p(wh), _p(bi), _p(bh), _p(H), B, T, D, Fh,
+                                    _RNN_ACTS[nonlinearity], _stream()), 'rnn_forward')
+        ctx.save_for_backward(xc, hc, wi, wh, H)
+        ctx.act, ctx.has_bias = _RNN_ACTS[nonlinearity], b_ih is not None
+        return H
+
+    @staticmethod
+    def backward(ctx, dH):
+        x, h0, wi, wh, H = ctx.saved_tensors
+        B, T, D = x.shape
+        Fh = wh.shape[0]
+        code = dtype_code(x.dtype)
+        slots = int(lib.gcrnn_rnn_wgrad_slots(code, B, T, D, Fh))
+        parts = torch.empty((slots, Fh, D + Fh + 1), dtype=x.dtype, device=x.device)
+        dZ = torch.empty_like(H)
+        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dHc = dH.contiguous().to(x.dtype)
+        check(lib.gcrnn_rnn_backward(code, _p(x), _p(h0), _p(wi), _p(wh), _p(H), _p(dHc), _p(dZ), _p(dh0), _p(dx), _p(parts), slots,
+                                     B, T, D, Fh, ctx.act, _stream()), 'rnn_backward')
+        dw = parts.sum(dim=0)
+        dwi, dwh = dw[:, :D], dw[:, D:D + Fh]
+        db = dw[:, D + Fh] if ctx.has_bias else None
+        return dx, dh0, dwi, dwh, db, (db.clone() if db is not None else None), None
+
+
+def _rnn_sequence_composed(x, h0, w_ih, w_hh, b_ih, b_hh, nonlinearity):
+    """The composed path outside the kernels' envelope: torch matmul + the activation, step by step, under autograd."""
+    act = torch.tanh if nonlinearity == 'tanh' else torch.relu
+    U = x.matmul(w_ih.t())
+    if b_ih is not None:
+        U = U + (b_ih + b_hh)
+    h, hs = h0, []
+    for t in range(x.shape[1]):
+        h = act(U[:, t] + h.matmul(w_hh.t()))
+        hs.append(h)
+    return torch.stack(hs, dim=1)
+
+
+def rnn_sequence(x, h0, w_ih, w_hh, b_ih, b_hh, nonlinearity):
+    """H [B][T][F_h] of h_t = act(W_ih x_t + b_ih + W_hh h_{t-1} + b_hh) for x [B][T][D], h0 [B][F_h], w_ih F_h x D, w_hh F_h x F_h,
+    b_ih / b_hh F_h (or both None), nonlinearity 'tanh' or 'relu'. x is computed in the parameters' dtype (bf16 activations with
+    fp32 parameters). The HIP kernels where rnn_supported says so, else the composed step-by-step path. CPU tensors raise."""
+    if nonlinearity not in _RNN_ACTS:
+        raise ValueError("Unknown nonlinearity '%s'. Select from 'tanh' or 'relu'." % (nonlinearity,))
+    assert (b_ih is None) == (b_hh is None)
+    require_device(x, h0, w_ih, w_hh, b_ih, b_hh)
+    assert x.dim() == 3 and h0.dim() == 2 and x.shape[2] == w_ih.shape[1] and h0.shape == (x.shape[0], w_hh.shape[0]), \
+        (tuple(x.shape), tuple(h0.shape), tuple(w_ih.shape), tuple(w_hh.shape))
+    x, h0 = x.to(w_ih.dtype), h0.to(w_ih.dtype)
+    B, T, D = x.shape
+    if rnn_supported(w_ih.dtype, B, T, D, w_hh.shape[0]):
+        return _RnnSequence.apply(x, h0, w_ih, w_hh, b_ih, b_hh, nonlinearity)
+    return _rnn_sequence_composed(x, h0, w_ih, w_hh, b_ih, b_hh, nonlinearity)
+
+
 # ------------------------------------------------------------------------------------------ loss
 class _L1Loss(torch.autograd.Function):
     """mean |x - y| with the gradient produced in the same pass (reference batchTimeL1Loss, miscTools.py:112-119)."""

@@ -737,6 +737,26 @@ int gcrnn_graph_filter_layer_backward(int dtype, const void* x, const void* w, c
                                       const void* val, double uniform_w, int64_t items, int64_t N, int64_t nnz, int64_t E,
                                       int64_t F_in, int64_t F_out, int64_t K, int act, void* stream);
 
+/* ==== plain RNN: the drivers' RNN baselines ======================================================================
+ * torch.nn.RNN(D, F_h, num_layers=1, nonlinearity, bias, batch_first=True) of the reference's RNNforRegression /
+ * RNNforClassification (architectures.py:1861-2149):  h_t = act( W_ih x_t + b_ih + W_hh h_{t-1} + b_hh ),  t = 1..T.
+ * x [B][T][D], h0 [B][F_h], w_ih [F_h][D], w_hh [F_h][F_h], b_ih / b_hh [F_h] (both or neither NULL), H [B][T][F_h], all
+ * contiguous of `dtype` (GCRNN_F32 or GCRNN_F64); act: 0 tanh, 1 ReLU.
+ * forward: two launches (the input projection into H, then all T steps of the recurrence in one launch); H is the only output.
+ * backward: dH [B][T][F_h] -> dZ [B][T][F_h] (workspace: dz_t = (dH_t + W_hh^T dz_{t+1}) * act'(h_t)), dh0 [B][F_h] (or NULL),
+ * dx [B][T][D] (or NULL: not computed), dw_parts [slots][F_h][D + F_h + 1] per-slot partial sums of [dW_ih | dW_hh | db]
+ * (db = db_ih = db_hh), every slot written, added by the caller in a fixed order (deterministic). At most three launches.
+ * supported: 1 <= F_h <= 64, 1 <= D <= 65536, B*T*(D + F_h + 1) < 2^31; the entry points return GCRNN_ERR_UNSUPPORTED otherwise,
+ * before any launch. slots must equal gcrnn_rnn_wgrad_slots(...) of the same problem (a function of the shape alone), else
+ * GCRNN_ERR_WORKSPACE. */
+int gcrnn_rnn_supported(int dtype, int64_t B, int64_t T, int64_t D, int64_t F_h);
+int64_t gcrnn_rnn_wgrad_slots(int dtype, int64_t B, int64_t T, int64_t D, int64_t F_h);
+int gcrnn_rnn_forward(int dtype, const void* x, const void* h0, const void* w_ih, const void* w_hh, const void* b_ih,
+                      const void* b_hh, void* H, int64_t B, int64_t T, int64_t D, int64_t F_h, int act, void* stream);
+int gcrnn_rnn_backward(int dtype, const void* x, const void* h0, const void* w_ih, const void* w_hh, const void* H, const void* dH,
+                       void* dZ, void* dh0, void* dx, void* dw_parts, int64_t slots, int64_t B, int64_t T, int64_t D, int64_t F_h,
+                       int act, void* stream);
+
 /* ==== training-loop loss ==========================================================================================
  * batchTimeL1Loss (Utils/miscTools.py:112-119 = nn.L1Loss: mean |x - y| over every entry) and its gradient in one pass.
  * x, y, grad: n contiguous elements of `dtype` (F32 / F64 / BF16), 16-byte aligned; grad (may be NULL) =
