@@ -10,6 +10,7 @@ stations) of the source. Same tensor shapes and model as the driver: x is B x T 
 
     python examples/epicenter_estimation.py [--seq 200] [--taps 3] [--steps 600] [--lr 5e-3] [--time-gating] [--dtype f64]
     python examples/epicenter_estimation.py --models Sel,GCRNNGNN,TimeGCRNNGNN
+    python examples/epicenter_estimation.py --trainer RMSprop --lr 1e-3 --lr-decay-rate 0.9 --lr-decay-period 1 --steps-per-epoch 100
 
 --models picks the driver's other models (epicenterEstimation.py:150-153, 180-196, 258-280): 'Sel' = SelectionGNN([T, 21], [taps],
 ReLU, NoPool, MLP [11]) on the window's T samples as node features, 'GCRNNGNN' / 'TimeGCRNNGNN' = the gated GCRNN with a
@@ -33,6 +34,7 @@ import gated_gcrnns_amd.Modules.architectures as archit
 import gated_gcrnns_amd.Utils.graphML as gml
 from gated_gcrnns_amd.Modules.train_rnn import train_step
 from gated_gcrnns_amd.Utils import dataTools
+from gated_gcrnns_amd.optim import TRAINERS, StepDecay, make_trainer
 
 
 def synthetic_waves(S, n, T, regions, rng):
@@ -63,6 +65,15 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=100)
     ap.add_argument('--steps', type=int, default=600)
     ap.add_argument('--lr', type=float, default=5e-3, help='the reference driver uses 1e-3 over many epochs')
+    ap.add_argument('--trainer', default='ADAM', choices=TRAINERS, help="the driver's `trainer` (epicenterEstimation.py, same block as the k-step driver)")
+    ap.add_argument('--beta1', type=float, default=0.9, help="Adam's beta1; RMSprop's alpha, as in the driver")
+    ap.add_argument('--beta2', type=float, default=0.999)
+    ap.add_argument('--optim', default='torch', choices=['flat', 'torch'], help='torch: the torch.optim class as in the reference driver; '
+                    'flat: optim.FlatAdam / FlatSGD / FlatRMSprop (one kernel over the flat parameter / gradient buffers)')
+    ap.add_argument('--lr-decay-rate', type=float, default=None, help="the driver's learningRateDecayRate (give both decay options to turn decay on)")
+    ap.add_argument('--lr-decay-period', type=int, default=None, help="the driver's learningRateDecayPeriod, in epochs")
+    ap.add_argument('--steps-per-epoch', type=int, default=None, help='this example draws --steps random batches without epochs: an "epoch" of the '
+                    'decay schedule is this many steps (default: all steps = one epoch); the schedule is stepped at the top of each, as in the reference')
     ap.add_argument('--time-gating', action='store_true')
     ap.add_argument('--rnn-features', type=int, default=21, help="RNNMLP's state features (the driver's rnnStateFeat)")
     ap.add_argument('--dtype', default='f64', choices=['f32', 'f64'])
@@ -105,10 +116,14 @@ def main(argv=None):
             model = archit.GatedGCRNNforClassification(1, args.features, args.taps, args.taps, torch.tanh, torch.nn.ReLU, [11], S, True,
                                                        time_gating=tg, spatial_gating=None, **head).to(dev)
             fwd = None
-        opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999))
+        opt = make_trainer(args.trainer, model.parameters(), args.lr, args.beta1, args.beta2, flat=args.optim == 'flat')
+        decay = StepDecay(opt, args.lr_decay_period, args.lr_decay_rate) if args.lr_decay_rate is not None and args.lr_decay_period is not None else None
+        per_epoch = args.steps_per_epoch or max(args.steps, 1)
         ce = torch.nn.CrossEntropyLoss()
         times, first, losses = [], None, []
         for it in range(args.steps):
+            if decay is not None and it % per_epoch == 0:
+                decay.step()                                             # top of the epoch, before its first batch (reference train_rnn.py:197-200)
             idx = torch.tensor(rng.choice(xtr.shape[0], args.batch, replace=False), device=dev)
             torch.cuda.synchronize(); t0 = time.perf_counter()
             loss, _ = train_step(model, ce, opt, xtr_d[idx], ytr_d[idx], args.features, forward=fwd)

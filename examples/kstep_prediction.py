@@ -5,7 +5,8 @@
     python examples/kstep_prediction.py [--nodes 80] [--taps 5] [--seq 5] [--epochs 1] [--dtype f64]
     python examples/kstep_prediction.py --nodes 1000 --features 64 --seq 32 --dtype bf16 --ntrain 1024 --batch 256 --sparse
 
-Defaults follow the reference driver (N=80 SBM 0.8/0.2, 5 taps, K=seqLen=5, F=20, batch 100, Adam 1e-3). --dtype bf16 feeds
+Defaults follow the reference driver (N=80 SBM 0.8/0.2, 5 taps, K=seqLen=5, F=20, batch 100, Adam 1e-3); --trainer ADAM|SGD|RMSprop,
+--lr, --beta1, --beta2, --lr-decay-rate and --lr-decay-period are the driver's training options (kStepPredGRNNs.py:158-172). --dtype bf16 feeds
 bf16 batches to fp32 master weights: all four variants (un-gated, time-, node- and edge-gated) then train on the fused kernels
 (N <= 1024, F in {32, 64}; other shapes: composed path in fp32). --sparse draws the BASELINE configs[1] graph (mean degree ~10).
 --models also accepts the driver's GNN models: 'Sel' (SelectionGNN([1, 8, 1], [10, 10], ReLU, NoPool), every time step a sample,
@@ -26,7 +27,7 @@ import gated_gcrnns_amd.Modules.architectures as archit
 import gated_gcrnns_amd.Utils.graphML as gml
 from gated_gcrnns_amd.Modules.train_rnn import MultipleModels, TrainableModel
 from gated_gcrnns_amd.Utils import dataTools, miscTools
-from gated_gcrnns_amd.optim import FlatAdam
+from gated_gcrnns_amd.optim import TRAINERS, make_trainer
 
 
 MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'NodeGCRNNMLP', 'EdgeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN', 'RNNMLP')
@@ -48,8 +49,15 @@ def main(argv=None):
                     help='comma-separated, of ' + ','.join(MODELS))
     ap.add_argument('--rnn-features', type=int, default=1, help="RNNMLP's state features (the driver's rnnStateFeat)")
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--optim', default='flat', choices=['flat', 'torch'], help='flat: optim.FlatAdam (one kernel over the flat '
-                    'parameter / gradient buffers); torch: torch.optim.Adam as in the reference driver')
+    ap.add_argument('--optim', default='flat', choices=['flat', 'torch'], help='flat: optim.FlatAdam / FlatSGD / FlatRMSprop (one kernel over '
+                    'the flat parameter / gradient buffers); torch: the torch.optim class as in the reference driver')
+    ap.add_argument('--trainer', default='ADAM', choices=TRAINERS, help="the driver's `trainer` (kStepPredGRNNs.py:158)")
+    ap.add_argument('--lr', type=float, default=1e-3, help="the driver's learningRate")
+    ap.add_argument('--beta1', type=float, default=0.9, help="Adam's beta1; RMSprop's alpha, as in the driver")
+    ap.add_argument('--beta2', type=float, default=0.999)
+    ap.add_argument('--lr-decay-rate', type=float, default=None, help="the driver's learningRateDecayRate (give both decay options to turn decay on)")
+    ap.add_argument('--lr-decay-period', type=int, default=None, help="the driver's learningRateDecayPeriod, in epochs; the schedule is stepped "
+                    'at the top of every epoch as in the reference')
     args = ap.parse_args(argv)
     unknown = [n for n in args.models.split(',') if n not in MODELS]
     if unknown:
@@ -72,10 +80,7 @@ def main(argv=None):
             continue
         m = archit.GatedGCRNNforRegression(1, args.features, args.taps, args.taps, torch.tanh, torch.nn.ReLU, [1], S, True,
                                            time_gating=tg, spatial_gating=sg, mlpType='multipMlp').to(dev)
-        if args.optim == 'flat':
-            opt = FlatAdam(m.parameters(), lr=1e-3, betas=(0.9, 0.999))          # kStepPredGRNNs.py:158-161
-        else:
-            opt = torch.optim.Adam(m.parameters(), lr=1e-3, betas=(0.9, 0.999))
+        opt = make_trainer(args.trainer, m.parameters(), args.lr, args.beta1, args.beta2, flat=args.optim == 'flat')      # kStepPredGRNNs.py:706-715
         models[name] = TrainableModel(m, miscTools.batchTimeL1Loss, opt, name, saveDir)
     for name in args.models.split(','):
         if name == 'Sel':
@@ -89,13 +94,13 @@ def main(argv=None):
         else:
             continue
         m = m.to(dev)
-        opt = FlatAdam(m.parameters(), lr=1e-3, betas=(0.9, 0.999)) if args.optim == 'flat' else \
-            torch.optim.Adam(m.parameters(), lr=1e-3, betas=(0.9, 0.999))
+        opt = make_trainer(args.trainer, m.parameters(), args.lr, args.beta1, args.beta2, flat=args.optim == 'flat')
         models[name] = TrainableModel(m, miscTools.batchTimeL1Loss, opt, name, saveDir)
     xT, yT = data.getSamples('train')
     xV, yV = data.getSamples('valid')
     out = MultipleModels(models, xT, yT, xV, yV, args.epochs, args.batch, data.seqLen, args.features,
-                         data.evaluate, validationInterval=5, rng=rng, doPrint=False, dataType=data_dt, rnnStateFeat=args.rnn_features)
+                         data.evaluate, validationInterval=5, rng=rng, doPrint=False, dataType=data_dt, rnnStateFeat=args.rnn_features,
+                         learningRateDecayRate=args.lr_decay_rate, learningRateDecayPeriod=args.lr_decay_period)
     xE, yE = data.getSamples('test')
     xE = xE.view(xE.shape[0], data.seqLen, -1).to(dev, data_dt).unsqueeze(2)
     yE = yE.view(yE.shape[0], data.seqLen, -1).to(dev, data_dt).unsqueeze(2)

@@ -7,11 +7,13 @@ batch-sharded data parallelism with one flat gradient all-reduce per step (paral
 """
 import os
 import time
+import warnings
 
 import numpy as np
 import torch
 
 from .. import ops
+from ..optim import StepDecay
 from ..parallel import FlatGradAllReduce, shard_range
 
 
@@ -38,7 +40,7 @@ def train_step(archit, loss_fn, optim, x, y, stateFeat, sync=None, weight=None, 
     archit(x, h0) with h0 = 0."""
     B = x.shape[0]
     if sync is None and hasattr(optim, 'sync'):
-        sync_z = optim.sync                      # optim.FlatAdam: the gradients live in its flat buffer
+        sync_z = optim.sync                      # optim.Flat*: the gradients live in its flat buffer
     else:
         sync_z = sync
     if sync_z is not None:
@@ -106,7 +108,8 @@ def _first_parameter(archit):
 
 
 def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSize, seqLen, stateFeat,
-                   evaluate, validationInterval=5, rank=0, world=1, doPrint=False, rng=None, dataType=None, rnnStateFeat=None):
+                   evaluate, validationInterval=5, rank=0, world=1, doPrint=False, rng=None, dataType=None, rnnStateFeat=None,
+                   learningRateDecayRate=None, learningRateDecayPeriod=None):
     """Train every model of `modelsDict` (name -> TrainableModel) on the same batches. Names containing 'GCRNN' are gated
     GCRNNs (archit(x, h0) on B x T x 1 x N); other names containing 'RNN' are the plain RNN baselines such as 'RNNMLP'
     (RNNforRegression: archit(x, h0, c0) on B x T x 1 x N with h0 = c0 = zeros(B, rnnStateFeat); rnnStateFeat=None takes the
@@ -117,6 +120,10 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
     (batchTimeMSELoss for k-step prediction). With world > 1 each rank takes its shard of every batch and the
     gradients are averaged by one flat all-reduce. dataType: dtype of the batches on the device (default: the parameters'
     dtype); torch.bfloat16 with fp32 parameters = bf16 activations over fp32 master weights (the fused kernels).
+    learningRateDecayRate, learningRateDecayPeriod: both given = learning-rate decay as in the reference (train_rnn.py:85-91, 149-155): one
+    optim.StepDecay per model (torch's StepLR for a torch.optim optimiser), stepped at the TOP of every epoch, before the first batch
+    (:197-200) -- a quirk of the reference that is reproduced, not fixed: with period 1 the very first epoch already trains at lr * rate.
+    A flat optimiser must keep its learning rate on the device (FlatSGD, FlatRMSprop, FlatAdam(device_lr=True); optim.make_trainer).
     Returns dicts of per-step loss / metric / seconds per model.
     """
     if rng is None:
@@ -138,8 +145,19 @@ def MultipleModels(modelsDict, xTrain, yTrain, xValid, yValid, nEpochs, batchSiz
     evalValid = {k: [] for k in modelsDict}
     timeTrain = {k: [] for k in modelsDict}
     best = {}
+    schedulers = {}
+    if learningRateDecayRate is not None and learningRateDecayPeriod is not None:
+        schedulers = {k: StepDecay(m.optim, learningRateDecayPeriod, learningRateDecayRate) for k, m in modelsDict.items()}
     for epoch in range(nEpochs):
         perm = [int(i) for i in rng.permutation(nTrain)]
+        if schedulers:
+            with warnings.catch_warnings():
+                # (torch's StepLR warns when it is stepped before the first optimiser step: that order is the reference's, kept on purpose)
+                warnings.filterwarnings('ignore', message='Detected call of `lr_scheduler.step\\(\\)` before `optimizer.step\\(\\)`')
+                for sched in schedulers.values():
+                    sched.step()
+            if doPrint and rank == 0:
+                print('Epoch %d, learning rate = %.8f' % (epoch + 1, sched.get_last_lr()[0]))       # reference train_rnn.py:207-208
         for b in range(len(sizes)):
             idx = perm[index[b]:index[b + 1]]
             nGlobal = len(idx)
@@ -195,8 +213,15 @@ class GraphedTrainStep(object):
 
     The reference's training configurations (N = 50..80 nodes, T = 5..20, batch 100; kStepPredGRNNs.py:110-127) are
     launch-bound on a GPU: a step is several hundred tiny kernels. Capturing the whole step removes the per-launch host
-    cost. Inputs are copied into static buffers; the optimiser is optim.FlatAdam (one kernel over the flat buffers, device step
-    counter: capturable as it is) or torch.optim.Adam created with capturable=True.
+    cost. Inputs are copied into static buffers; the optimiser is optim.FlatAdam / FlatSGD / FlatRMSprop (one kernel over the flat buffers,
+    device step counter: capturable as they are) or torch.optim.Adam created with capturable=True.
+
+    Learning-rate decay under capture: a `set_lr` / `optim.StepDecay.step()` between two calls takes effect on the next replay, in the one- and
+    the two-graph form, for the flat optimisers whose learning rate is on the DEVICE -- FlatSGD, FlatRMSprop and FlatAdam(device_lr=True)
+    (what optim.make_trainer(flat=True) returns): their kernels read it from a device scalar, and the fill that rewrites it is ordered on the
+    replay stream. It does NOT for FlatAdam() (the default, device_lr=False: the learning rate is a launch argument that the capture baked in;
+    its set_lr raises), nor for a torch.optim optimiser whose `lr` is a Python float (a StepLR then changes a value that no replay reads);
+    building one with a tensor `lr` and capturable=True is the caller's business.
 
     One process (`sync=None`): ONE graph holds the whole step. Batch-sharded over several ranks (`sync` = the parallel.FlatGradAllReduce whose
     views are the parameters' `.grad`, `optim.sync` for FlatAdam): TWO graphs -- [zero_grad, forward, loss, BPTT] and [optimiser step] -- with the
@@ -216,8 +241,8 @@ class GraphedTrainStep(object):
         self.sync, self.weight = sync, weight
         B, N = x.shape[0], x.shape[3]
         self.h0 = torch.zeros(B, stateFeat, N, dtype=x.dtype, device=x.device)
-        self.flat = hasattr(self.optim, 'sync')          # optim.FlatAdam: gradients are views of one flat buffer, step counter on the device
-        assert sync is None or self.flat and sync is self.optim.sync or not self.flat, 'FlatAdam reduces its own flat buffer: pass sync=optim.sync'
+        self.flat = hasattr(self.optim, 'sync')          # optim.Flat*: gradients are views of one flat buffer, step counter on the device
+        assert sync is None or self.flat and sync is self.optim.sync or not self.flat, 'a flat optimiser reduces its own flat buffer: pass sync=optim.sync'
         self.captured = x.device.type == 'cuda'
         if not self.captured:
             self.graph = self.graph_step = None

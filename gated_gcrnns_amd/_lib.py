@@ -61,6 +61,10 @@ def _bind(lib):
         'gcrnn_batch_time_mse': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p]),
         'gcrnn_adam_flat': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_double, _c_p, _c_p]),
+        'gcrnn_adam_flat_dlr': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, _c_p, _c_p]),
+        'gcrnn_sgd_flat': (C.c_int, [C.c_int, _c_p, _c_p, _c_i64, _c_p, C.c_double, _c_p]),
+        'gcrnn_rmsprop_flat': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_i64, _c_p, C.c_double, C.c_double, C.c_double, _c_p]),
         'gcrnn_taps_forward': (C.c_int, [C.c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, C.c_double, _c_p,
                                          _c_i64, _c_i64, _c_i64, _c_i64, C.c_int, _c_p]),
         'gcrnn_taps_backward_data': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_i64,

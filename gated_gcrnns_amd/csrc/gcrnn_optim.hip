@@ -5,6 +5,13 @@
 //   (parallel.FlatGradAllReduce) -- instead of ~10 launches per parameter tensor:
 //       m = b1 m + (1 - b1) g;   v = b2 v + (1 - b2) g^2;   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //   t is read from a DEVICE counter that the call increments first (hipGraph-capturable: no host value baked in).
+// gcrnn_adam_flat_dlr: the same step with the learning rate read from a DEVICE double (cast to the buffer type in the kernel), so
+//   that learning-rate decay (the drivers' StepLR, train_rnn.py:149-155, 197-200) reaches a step that was captured in a hipGraph.
+// gcrnn_sgd_flat: torch.optim.SGD(lr) as the drivers build it (kStepPredGRNNs.py:710-711: no momentum, no weight decay) in ONE
+//   launch:  p -= lr (g * grad_scale);  lr from a device double.
+// gcrnn_rmsprop_flat: torch.optim.RMSprop(lr, alpha) (kStepPredGRNNs.py:712-714; eps 1e-8, no momentum, not centered) in ONE launch,
+//   torch's operation order:  v = alpha v + (1 - alpha) g g;  p -= lr * (g / (sqrt(v) + eps));  lr from a device double.
+//   All three are element-wise passes without atomics or reductions: two runs give the same bits.
 // gcrnn_batch_time_mse: the drivers' metric batchTimeMSELoss (Utils/miscTools.py:121-130): for x, y as [R][C] matrices
 //   (R = batch * time rows, C = N * F columns)  mean_c sqrt(sum_r (x - y)^2) / sqrt(sum_r y^2)  in two launches
 //   (column partial sums over row slabs, then a fixed-order finish) instead of seven torch passes.
@@ -14,11 +21,10 @@ namespace {
 
 __global__ void adam_tick_kernel(int64_t* step) { step[0] += 1; }
 
+// element i of the Adam step; shared by the host-lr and the device-lr kernel, so that the two are one optimiser bit for bit
 template <typename T>
-__global__ __launch_bounds__(256) void adam_flat_kernel(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m, T* __restrict__ v,
-                                                        int64_t n, T lr, T b1, T b2, T eps, T gscale, const int64_t* __restrict__ step) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void adam_update(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, int64_t i, T lr,
+                                            T b1, T b2, T eps, T gscale, const int64_t* __restrict__ step) {
   const double t = (double)step[0];
   const T bc1 = (T)(1.0 - pow((double)b1, t)), bc2s = (T)sqrt(1.0 - pow((double)b2, t));
   const T gi = g[i] * gscale;
@@ -28,6 +34,43 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(T* __restrict__ p, const
   v[i] = vi;
   const T denom = (T)sqrt((double)vi) / bc2s + eps;
   p[i] -= (lr / bc1) * (mi / denom);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void adam_flat_kernel(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m, T* __restrict__ v,
+                                                        int64_t n, T lr, T b1, T b2, T eps, T gscale, const int64_t* __restrict__ step) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  adam_update<T>(p, g, m, v, i, lr, b1, b2, eps, gscale, step);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void adam_flat_dlr_kernel(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m, T* __restrict__ v,
+                                                            int64_t n, const double* __restrict__ lr_dev, T b1, T b2, T eps, T gscale,
+                                                            const int64_t* __restrict__ step) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  adam_update<T>(p, g, m, v, i, (T)lr_dev[0], b1, b2, eps, gscale, step);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sgd_flat_kernel(T* __restrict__ p, const T* __restrict__ g, int64_t n, const double* __restrict__ lr_dev,
+                                                       T gscale) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  p[i] -= (T)lr_dev[0] * (g[i] * gscale);                  // param.add_(grad, alpha=-lr)
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rmsprop_flat_kernel(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ v, int64_t n,
+                                                           const double* __restrict__ lr_dev, T alpha, T eps, T gscale) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const T gi = g[i] * gscale;
+  const T vi = v[i] * alpha + (T(1) - alpha) * gi * gi;    // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+  v[i] = vi;
+  const T avg = (T)sqrt((double)vi) + eps;                 // square_avg.sqrt().add_(eps)
+  p[i] -= (T)lr_dev[0] * (gi / avg);                       // param.addcdiv_(grad, avg, value=-lr)
 }
 
 // column partial sums of (x - y)^2 and y^2 over a slab of rows; thread = column (coalesced along the row)
@@ -88,6 +131,54 @@ extern "C" int gcrnn_adam_flat(int dtype, void* p, const void* g, void* m, void*
                                                                        eps, grad_scale, step_dev);
   else
     return GCRNN_ERR_BAD_DTYPE;
+  GCRNN_CHECK_LAUNCH();
+  return GCRNN_OK;
+}
+
+extern "C" int gcrnn_adam_flat_dlr(int dtype, void* p, const void* g, void* m, void* v, int64_t n, const double* lr_dev, double beta1,
+                                   double beta2, double eps, double grad_scale, int64_t* step_dev, void* stream) {
+  if (!p || !g || !m || !v || !lr_dev || !step_dev) return GCRNN_ERR_NULL_POINTER;
+  if (n <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  hipStream_t st = as_stream(stream);
+  GCRNN_PRE_LAUNCH();
+  adam_tick_kernel<<<1, 1, 0, st>>>(step_dev);
+  if (dtype == GCRNN_F32)
+    adam_flat_dlr_kernel<float><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((float*)p, (const float*)g, (float*)m, (float*)v, n, lr_dev, (float)beta1,
+                                                                          (float)beta2, (float)eps, (float)grad_scale, step_dev);
+  else
+    adam_flat_dlr_kernel<double><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((double*)p, (const double*)g, (double*)m, (double*)v, n, lr_dev, beta1,
+                                                                           beta2, eps, grad_scale, step_dev);
+  GCRNN_CHECK_LAUNCH();
+  return GCRNN_OK;
+}
+
+extern "C" int gcrnn_sgd_flat(int dtype, void* p, const void* g, int64_t n, const double* lr_dev, double grad_scale, void* stream) {
+  if (!p || !g || !lr_dev) return GCRNN_ERR_NULL_POINTER;
+  if (n <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  hipStream_t st = as_stream(stream);
+  GCRNN_PRE_LAUNCH();
+  if (dtype == GCRNN_F32)
+    sgd_flat_kernel<float><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((float*)p, (const float*)g, n, lr_dev, (float)grad_scale);
+  else
+    sgd_flat_kernel<double><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((double*)p, (const double*)g, n, lr_dev, grad_scale);
+  GCRNN_CHECK_LAUNCH();
+  return GCRNN_OK;
+}
+
+extern "C" int gcrnn_rmsprop_flat(int dtype, void* p, const void* g, void* v, int64_t n, const double* lr_dev, double alpha, double eps,
+                                  double grad_scale, void* stream) {
+  if (!p || !g || !v || !lr_dev) return GCRNN_ERR_NULL_POINTER;
+  if (n <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  hipStream_t st = as_stream(stream);
+  GCRNN_PRE_LAUNCH();
+  if (dtype == GCRNN_F32)
+    rmsprop_flat_kernel<float><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((float*)p, (const float*)g, (float*)v, n, lr_dev, (float)alpha, (float)eps,
+                                                                         (float)grad_scale);
+  else
+    rmsprop_flat_kernel<double><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((double*)p, (const double*)g, (double*)v, n, lr_dev, alpha, eps, grad_scale);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }

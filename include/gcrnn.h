@@ -780,6 +780,21 @@ int gcrnn_batch_time_mse(int dtype, const void* x, const void* y, void* part, vo
  * (capturable: no host value is baked into the launch). */
 int gcrnn_adam_flat(int dtype, void* p, const void* g, void* m, void* v, int64_t n, double lr, double beta1, double beta2,
                     double eps, double grad_scale, int64_t* step_dev, void* stream);
+/* The drivers' other trainers and learning-rate decay (`trainer`, kStepPredGRNNs.py:158-161, built at :706-715;
+ * `doLearningRateDecay`, a StepLR stepped at the top of every epoch, Modules/train_rnn.py:149-155, 197-200). In these three
+ * the learning rate is read from ONE device double `lr_dev` and cast to the buffer type inside the kernel: nothing that
+ * decay changes is a launch argument, so a step captured in a hipGraph follows a later write to lr_dev. Same buffers,
+ * grad_scale, argument checks and status codes as gcrnn_adam_flat; element-wise, no atomics: two runs give the same bits.
+ * gcrnn_adam_flat_dlr replaces torch.optim.Adam(lr, betas).step() under a StepLR: gcrnn_adam_flat's arithmetic in the same
+ *   order with the same device step counter (two launches: the counter tick and the pass).
+ * gcrnn_sgd_flat replaces torch.optim.SGD(lr).step() (no momentum, no weight decay) in one launch: p -= lr (g grad_scale).
+ * gcrnn_rmsprop_flat replaces torch.optim.RMSprop(lr, alpha = beta1).step() (eps 1e-8, no momentum, not centered) in one
+ *   launch: v = alpha v + (1 - alpha) g g;  p -= lr g / (sqrt(v) + eps), in torch's operation order. */
+int gcrnn_adam_flat_dlr(int dtype, void* p, const void* g, void* m, void* v, int64_t n, const double* lr_dev, double beta1,
+                        double beta2, double eps, double grad_scale, int64_t* step_dev, void* stream);
+int gcrnn_sgd_flat(int dtype, void* p, const void* g, int64_t n, const double* lr_dev, double grad_scale, void* stream);
+int gcrnn_rmsprop_flat(int dtype, void* p, const void* g, void* v, int64_t n, const double* lr_dev, double alpha, double eps,
+                       double grad_scale, void* stream);
 
 /* ==== edge gate: graph attention on the CSR support of S + I ====================================================
  * Replaces graphAttention (graphML.py:521-627: dense B x N x N scores, mask, softmax, weighted sum) inside
