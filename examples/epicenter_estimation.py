@@ -11,6 +11,12 @@ stations) of the source. Same tensor shapes and model as the driver: x is B x T 
     python examples/epicenter_estimation.py [--seq 200] [--taps 3] [--steps 600] [--lr 5e-3] [--time-gating] [--dtype f64]
     python examples/epicenter_estimation.py --models Sel,GCRNNGNN,TimeGCRNNGNN
     python examples/epicenter_estimation.py --trainer RMSprop --lr 1e-3 --lr-decay-rate 0.9 --lr-decay-period 1 --steps-per-epoch 100
+    python examples/epicenter_estimation.py --loss hip --harness --epochs 6 --valid-interval 10
+
+--loss hip takes the loss, its gradient and the accuracy from the one-pass HIP cross-entropy kernel (Utils/miscTools.crossEntropyLoss /
+accuracy) instead of torch.nn.CrossEntropyLoss and an argmax on the host. --harness trains through the driver's own harness,
+Modules/train_rnn_quake.MultipleModels (epochs over the training windows in batches of --batch, validation every --valid-interval steps on
+one half of the held-out windows, Best / Last checkpoints), then runs its test phase (evaluate_checkpoints) on the other half.
 
 --models picks the driver's other models (epicenterEstimation.py:150-153, 180-196, 258-280): 'Sel' = SelectionGNN([T, 21], [taps],
 ReLU, NoPool, MLP [11]) on the window's T samples as node features, 'GCRNNGNN' / 'TimeGCRNNGNN' = the gated GCRNN with a
@@ -32,26 +38,36 @@ import torch
 
 import gated_gcrnns_amd.Modules.architectures as archit
 import gated_gcrnns_amd.Utils.graphML as gml
+from gated_gcrnns_amd.Modules import train_rnn_quake
 from gated_gcrnns_amd.Modules.train_rnn import train_step
+from gated_gcrnns_amd.Utils import miscTools
 from gated_gcrnns_amd.Utils import dataTools
 from gated_gcrnns_amd.optim import TRAINERS, StepDecay, make_trainer
 
 
-def synthetic_waves(S, n, T, regions, rng):
-    """Sensor noise everywhere; a few steps before the end of the window a pulse is released at the source station and
-    spreads as x_{t+1} = 0.95 x_t S (a linear diffusion like dataTools.py:1282-1302): the last samples carry the arrival
-    pattern, as in the reference's windows (the last seqLen samples of a recording, dataTools.py:1471)."""
-    N = S.shape[0]
-    src = rng.integers(0, N, size=n)
-    t0 = rng.integers(max(T - 12, 0), max(T - 3, 1), size=n)
-    x = 0.02 * rng.standard_normal((n, T, N))
-    cur = np.zeros((n, N))
-    for t in range(T):
-        cur = 0.95 * cur @ S
-        hit = t0 == t
-        cur[hit, src[hit]] += 5.0 * (1.0 + 0.1 * rng.standard_normal(int(hit.sum())))
-        x[:, t] += cur
-    return x, regions[src]
+synthetic_waves = dataTools.synthetic_waves
+
+
+def run_harness(args, name, model, loss, opt, xtr, ytr, xte, yte):
+    """The driver's training and test phases (epicenterEstimation.py:1128-1245) on the synthetic windows."""
+    import tempfile
+    evaluate = miscTools.accuracy if args.loss == 'hip' else \
+        (lambda yHat, y: (yHat.argmax(dim=1) == y.reshape(-1)).to(torch.float64).mean())
+    half = xte.shape[0] // 2
+    tm = train_rnn_quake.TrainableModel(model, loss, opt, name, args.save_dir or tempfile.mkdtemp(prefix='epicenter_'))
+    kw = dict(stateFeat=args.features, evaluate=evaluate, rnnStateFeat=args.rnn_features)
+    out = train_rnn_quake.MultipleModels({name: tm}, torch.tensor(xtr), torch.tensor(ytr), torch.tensor(xte[:half]), torch.tensor(yte[:half]),
+                                         nEpochs=args.epochs, batchSize=args.batch, seqLen=args.seq, validationInterval=args.valid_interval,
+                                         learningRateDecayRate=args.lr_decay_rate, learningRateDecayPeriod=args.lr_decay_period, **kw)
+    test = train_rnn_quake.evaluate_checkpoints({name: tm}, torch.tensor(xte[half:]), torch.tensor(yte[half:]), seqLen=args.seq, **kw)
+    losses = out['lossTrain'][name]
+    ms = 1e3 * float(np.median(out['timeTrain'][name][3:]))
+    print('%s classification through the harness, T=%d %s, %d steps: loss %.3f -> %.3f, best validation accuracy %.3f (step %d), test accuracy '
+          'Best %.3f / Last %.3f (chance %.3f), median %.2f ms/step' % (name, args.seq, args.dtype, len(losses), losses[0], losses[-1],
+                                                                         out['bestScore'][name], out['bestStep'][name], test['Best'][name],
+                                                                         test['Last'][name], 1 / 11, ms))
+    return {'loss': losses, 'accuracy': test['Last'][name], 'ms_per_step': ms, 'best_accuracy': test['Best'][name],
+            'last_accuracy': test['Last'][name]}
 
 
 MODELS = ('GCRNNMLP', 'TimeGCRNNMLP', 'Sel', 'GCRNNGNN', 'TimeGCRNNGNN', 'RNNMLP')
@@ -78,6 +94,12 @@ def main(argv=None):
     ap.add_argument('--rnn-features', type=int, default=21, help="RNNMLP's state features (the driver's rnnStateFeat)")
     ap.add_argument('--dtype', default='f64', choices=['f32', 'f64'])
     ap.add_argument('--models', default=None, help='comma-separated, of ' + ','.join(MODELS) + ' (default: one MLP-head GCRNN)')
+    ap.add_argument('--loss', default='torch', choices=['torch', 'hip'], help='torch: nn.CrossEntropyLoss and a host argmax; hip: the one-pass '
+                    'cross-entropy kernel for loss, gradient and accuracy')
+    ap.add_argument('--harness', action='store_true', help='train through Modules/train_rnn_quake.MultipleModels and test its Best / Last checkpoints')
+    ap.add_argument('--epochs', type=int, default=3, help='--harness: epochs over the training windows (instead of --steps random batches)')
+    ap.add_argument('--valid-interval', type=int, default=10, help="--harness: the driver's validationInterval, in steps")
+    ap.add_argument('--save-dir', default=None, help='--harness: where the checkpoints go (default: a temporary directory)')
     args = ap.parse_args(argv)
     names = args.models.split(',') if args.models else ['TimeGCRNNMLP' if args.time_gating else 'GCRNNMLP']
     if any(n not in MODELS for n in names):
@@ -119,7 +141,10 @@ def main(argv=None):
         opt = make_trainer(args.trainer, model.parameters(), args.lr, args.beta1, args.beta2, flat=args.optim == 'flat')
         decay = StepDecay(opt, args.lr_decay_period, args.lr_decay_rate) if args.lr_decay_rate is not None and args.lr_decay_period is not None else None
         per_epoch = args.steps_per_epoch or max(args.steps, 1)
-        ce = torch.nn.CrossEntropyLoss()
+        ce = miscTools.CrossEntropyLoss() if args.loss == 'hip' else torch.nn.CrossEntropyLoss()
+        if args.harness:
+            results[name] = run_harness(args, name, model, ce, opt, xtr, ytr, xte, yte)
+            continue
         times, first, losses = [], None, []
         for it in range(args.steps):
             if decay is not None and it % per_epoch == 0:
@@ -138,7 +163,10 @@ def main(argv=None):
                 logits = model(xe, h0, h0)
             else:
                 logits = model(xe, torch.zeros(xe.shape[0], args.features, N, dtype=dt, device=dev))
-            acc = float((logits.argmax(dim=1).cpu() == torch.tensor(yte)).double().mean())
+            if args.loss == 'hip':
+                acc = float(miscTools.accuracy(logits, torch.tensor(yte, device=dev)))
+            else:
+                acc = float((logits.argmax(dim=1).cpu() == torch.tensor(yte)).double().mean())
         ms = 1e3 * float(np.median(times[3:]))
         print('%s classification N=%d T=%d K=%d F=%d %s: loss %.3f -> %.3f, test accuracy %.3f (chance %.3f), '
               'median %.2f ms/step (%.0f seq/s)' % (name, N, args.seq, args.taps, args.features, args.dtype, first, float(loss), acc,

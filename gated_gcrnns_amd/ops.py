@@ -3110,6 +3110,104 @@ def batch_time_mse(xv, yv):
     return out[0]
 
 
+CROSS_ENTROPY_MAX_CLASSES = 1024                   # GCRNN_CROSS_ENTROPY_MAX_CLASSES: a row lives in one wave's registers
+_CE_DTYPES = (torch.float32, torch.float64, torch.bfloat16)
+
+
+def cross_entropy_supported(logits):
+    """Whether gcrnn_cross_entropy takes these logits: a device matrix [B][C] of f32 / f64 / bf16 with 1 <= C <= 1024, B >= 1."""
+    return bool(logits.is_cuda and logits.dim() == 2 and logits.dtype in _CE_DTYPES and logits.shape[0] >= 1
+                and 1 <= logits.shape[1] <= CROSS_ENTROPY_MAX_CLASSES)
+
+
+def _ce_labels(labels, B):
+    """int64 labels [B] from int64 or from a floating tensor that holds integers (the reference's dataset keeps labels in the data type
+    and casts per batch, train_rnn_quake.py:220), B or B x 1."""
+    lab = labels.reshape(-1)
+    assert lab.numel() == B, (tuple(labels.shape), B)
+    return lab.to(torch.int64).contiguous()
+
+
+def _ce_launch(zc, lab, want_grad):
+    """(loss, hits, grad): 0-dim views of the launch's scratch (accumulation dtype / int64) and the gradient (or None)."""
+    B, Cc = zc.shape
+    nb = int(lib.gcrnn_cross_entropy_blocks(B, Cc))
+    fbuf = torch.empty((nb + 1,), dtype=torch.float64 if zc.dtype == torch.float64 else torch.float32, device=zc.device)
+    ibuf = torch.empty((nb + 1,), dtype=torch.int64, device=zc.device)            # [0, nb): per-block sums; [nb]: the result
+    grad = torch.empty_like(zc) if want_grad else None
+    check(lib.gcrnn_cross_entropy(dtype_code(zc.dtype), _p(zc), _p(lab), _p(grad), _p(fbuf), _p(ibuf),
+                                  C.c_void_p(fbuf.data_ptr() + nb * fbuf.element_size()), C.c_void_p(ibuf.data_ptr() + nb * 8),
+                                  B, Cc, 1.0 / B, _stream()), 'cross_entropy')
+    return fbuf[nb], ibuf[nb], grad
+
+
+class _CrossEntropy(torch.autograd.Function):
+    """nn.CrossEntropyLoss() (mean, no weights) with the gradient and the argmax hit count produced by the same launch."""
+
+    @staticmethod
+    def forward(ctx, logits, lab):
+        zc = logits.contiguous()
+        want = ctx.needs_input_grad[0]
+        loss, hits, grad = _ce_launch(zc, lab, want)
+        ctx.grad = grad
+        ctx.used = False
+        ctx.operands = (zc, lab) if want else None     # (references: a second backward recomputes the gradient from them)
+        ctx.mark_non_differentiable(hits)
+        return loss, hits                              # (the accumulation dtype: fp32 for bf16 logits -- a bf16 loss would drop 16 of its bits)
+
+    @staticmethod
+    def backward(ctx, gout, _ghits):
+        if ctx.operands is None:
+            return None, None
+        if ctx.used:
+            # (as _L1Loss: the buffer was scaled in place and handed out by the first backward; a second backward over a retained graph gets a
+            #  FRESH gradient from the saved operands, scaled by its own upstream)
+            zc, lab = ctx.operands
+            g = _ce_launch(zc, lab, True)[2]
+        else:
+            g, ctx.grad = ctx.grad, None               # handed out: the only reference left is the caller's (AccumulateGrad may keep it as .grad)
+        ctx.used = True
+        r = gout.detach().to(torch.float64 if g.dtype == torch.float64 else torch.float32).reshape(1).contiguous()
+        if g.data_ptr() % 16 == 0:
+            check(lib.gcrnn_scale_unless_one(dtype_code(g.dtype), _p(g), _p(r), g.numel(), _stream()), 'scale_unless_one')
+        else:
+            g.mul_(r.to(g.dtype))
+        return g, None
+
+
+def cross_entropy(logits, labels, return_hits=False):
+    """Mean cross-entropy of logits [B][C] against integer labels [B] (int64, or a floating tensor holding integers) =
+    torch.nn.CrossEntropyLoss() with its defaults, on the one-pass HIP kernel; differentiable in the logits; a 0-dim device tensor in
+    the logits' dtype (fp32 for bf16 logits: the accumulation type). return_hits=True also
+    returns the number of rows whose argmax (first maximal index) equals the label, a 0-dim int64 device tensor of the SAME launch.
+    Labels outside [0, C) -- ignore_index = -100 included: not supported -- give a NaN loss and NaN gradient rows. Logits the kernel
+    does not take (see cross_entropy_supported; C > 1024, other dtypes) go through torch's own expressions."""
+    require_device(logits, labels)
+    assert logits.dim() == 2, tuple(logits.shape)
+    lab = _ce_labels(labels, logits.shape[0])
+    if cross_entropy_supported(logits):
+        loss, hits = _CrossEntropy.apply(logits, lab)
+    else:
+        loss = torch.nn.functional.cross_entropy(logits, lab)
+        hits = (torch.argmax(logits.detach(), dim=1) == lab).sum() if return_hits else None
+    return (loss, hits) if return_hits else loss
+
+
+def accuracy(logits, labels):
+    """Fraction of rows whose argmax (first maximal index, torch.argmax's rule) equals the label (reference QuakeData.evaluate,
+    dataTools.py:1564-1586): the cross-entropy kernel without a gradient. 0-dim device tensor, fp64 for fp64 logits, else fp32."""
+    require_device(logits, labels)
+    assert logits.dim() == 2, tuple(logits.shape)
+    B = logits.shape[0]
+    lab = _ce_labels(labels, B)
+    out_dt = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    if cross_entropy_supported(logits):
+        hits = _ce_launch(logits.detach().contiguous(), lab, False)[1]
+    else:
+        hits = (torch.argmax(logits.detach(), dim=1) == lab).sum()
+    return hits.to(out_dt) / B
+
+
 # ------------------------------------------------------------------------------------------ row-linear layers
 class _RowLinear(torch.autograd.Function):
     """y = x W^T (+ b) over a huge number of rows (x: R x in; R = T*N*B node-rows of the per-node head and of the

@@ -772,6 +772,21 @@ int gcrnn_scale_unless_one(int dtype, void* data, const void* r, int64_t n, void
  * gcrnn_batch_time_mse_slabs(R, C) * 2 * C accumulators (fp64 for F64, else fp32); out: one accumulator. Deterministic. */
 int64_t gcrnn_batch_time_mse_slabs(int64_t R, int64_t C);
 int gcrnn_batch_time_mse(int dtype, const void* x, const void* y, void* part, void* out, int64_t R, int64_t C, void* stream);
+/* The epicenter-estimation driver's loss and metric: nn.CrossEntropyLoss() with its defaults (mean over the batch, no class
+ * weights; epicenterEstimation.py) and QuakeData.evaluate's argmax accuracy (Utils/dataTools.py:1564-1586) in ONE pass over
+ * logits [B][C] (contiguous, F32 / F64 / BF16), labels [B] int64. One row per 64-lane wave, read once:
+ *   loss_out[0] = inv_B * sum_b (lse_b - z[b][label_b])     (fp32 for F32 / BF16, fp64 for F64; accurate exp / log)
+ *   grad[b][c]  = (softmax(z[b])[c] - [c == label_b]) * inv_B, in the logits' dtype (grad may be NULL: no gradient)
+ *   hits_out[0] = number of rows whose FIRST maximal index (torch.argmax's rule) equals the label
+ * partial / hit_partial: gcrnn_cross_entropy_blocks(B, C) accumulators / int64 of scratch (per-block sums, added by a second
+ * launch in a fixed order: deterministic, no atomics). No host synchronisation, no allocation: capturable.
+ * A label outside [0, C) -- torch's ignore_index = -100 included, which is NOT supported -- never indexes anything: that row's
+ * loss and gradient row are NaN and it is not a hit. 1 <= C <= GCRNN_CROSS_ENTROPY_MAX_CLASSES, else GCRNN_ERR_UNSUPPORTED
+ * (gcrnn_cross_entropy_blocks returns 0). class weights, label smoothing: not supported. */
+#define GCRNN_CROSS_ENTROPY_MAX_CLASSES 1024
+int64_t gcrnn_cross_entropy_blocks(int64_t B, int64_t C);
+int gcrnn_cross_entropy(int dtype, const void* logits, const int64_t* labels, void* grad, void* partial, int64_t* hit_partial,
+                        void* loss_out, int64_t* hits_out, int64_t B, int64_t C, double inv_B, void* stream);
 
 /* ==== optimiser ====================================================================================================
  * torch.optim.Adam (kStepPredGRNNs.py:158-161, stepped at train_rnn.py:276) over ONE flat parameter / gradient / moment
