@@ -141,6 +141,7 @@ struct Seq32Args {
   const float* ng0; int64_t ngstride; int64_t nghalf;  // ng0 + step ngstride: ni [B][N] fp32, nf = + nghalf; optional scalar time gates gi0 / gf0 (+ step gstride)
   const float* r1a; const float* r1b;                  // R1 (rank-1-weighted graph S[m][n] = a[m] b[n], plan of its 0/1 pattern): the factors [NP] fp32, zero for padding rows
   int stagger;                                         // > 0: workgroup i starts ((i / 8) % 8) * stagger shader cycles late (de-synchronises the CUs' memory phases for the whole launch)
+  uint16_t* scr;                                       // VAR bit 2: the state scratch [workgroups][HS-1][NP slots][32] bf16 (out0 is null: no state image)
 };
 
 // this lane's id, re-derived where it is needed (two VALU instructions; volatile: neither hoisted nor kept): anything derived from the
@@ -192,6 +193,16 @@ struct Seq32Map {
 // VAR: bit 0 = the launch lays out the input itself (inline pack), bit 1 = it writes the user-layout output. Compile-time so that every way
 // the forward is issued -- as the module issues it (3), caller-packed X (2), sequence-major in and out (0) -- is a kernel symbol of its own in a
 // trace (profiles/*kernel_stats.csv reproduce the bench line's roofline fraction), and the paths not taken cost neither code nor registers.
+// Bit 2 (with bit 1, MODE 0, persistent form: inference, where H leaves through the user-layout tile and nobody reads the sequence-major state
+// image): no state image at all. The only state bytes this launch reads back are chunks 0 .. HS-2 of h_t, one step later (chunk HS-1 is handed
+// over in registers): they go to a scratch of this WORKGROUP, [HS-1][NP][32] bf16 in SLOT order (row = (wave * STILES + tile) * 16 + r), so a
+// wave-instruction stores -- and later loads -- 1 KB of contiguous bytes instead of sixteen half-used 128-byte lines of [node][F] rows, and
+// neither side needs the slot table. Chunk HS-1 is not stored to memory (at HS = 1 nothing is stored or reloaded); step 0 reads h0 as before.
+// ONE buffer for all steps and sequences of the workgroup: a lane reloads exactly the 16 bytes it stored itself. In its program order the
+// reload of step t (requested in the last chunk's epilogue) has been consumed by the seed's MFMAs of step t+1 -- which wait for it -- before
+// chunk 0's epilogue of step t+1 stores to the address again, and that store has retired behind the vmcnt(0) of every later hop before the
+// next reload is requested. The addresses are re-used every step, so the reload carries sc1: it is served by L2 (where the line comes from
+// anyway, a step after its store) whatever this CU's vector L1 still holds of the previous step's line.
 // MODE 0: the recurrence (GATED: with the scalar time gates gi_t, gf_t known before step 0 -- they read (x_t, h0), never h_{t-1}).
 // MODE 1: the time gates' pre-pass for BOTH gates at once: an item (t, b) is one "sequence" of one step whose cell has 2 F outputs -- chunks
 //         0 .. F/32-1 the input gate's sub-cell, the rest the forget gate's (weights and biases concatenated by the caller) -- so the operand
@@ -212,6 +223,9 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   constexpr bool ITEMS = (MODE == 1 || MODE == 3);      // one-step items (t, b) instead of sequences
   constexpr bool SONLY = (MODE == 2 || MODE == 4);      // state-only operand that is this launch's own output (XS = 0)
   constexpr bool PKV = (VAR & 1) != 0, USERV = (VAR & 2) != 0 && (MODE == 0 || MODE == 4);
+  constexpr bool SCRV = (VAR & 4) != 0;      // state scratch in slot order, no state image
+  static_assert(!SCRV || (MODE == 0 && !SPLIT && (VAR & 2) != 0), "state scratch: the persistent forward with the user-layout output");
+  constexpr int SCR_CH = NP * 64;            // bytes of one chunk's scratch rows [NP slots][32] bf16
   static_assert(MODE == 0 || ((MODE >= 1 && MODE <= 4) && !GATED), "modes");
   static_assert(MODE < 3 || (!R1 && !SPLIT), "modes 3, 4: uniform-weight graphs, persistent form");
   using M = Seq32Map<K, HS, XS>;
@@ -754,6 +768,10 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       // ---- epilogue: + 2 b, tanh, bf16; lane (r, q) holds features 32 c + 8 q .. + 7 of its node: ONE 16-byte store per tile ------------
       typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4_t;
       const int lane = lane_now(), q = lane >> 4, tl = wave * 64 + lane;
+      // VAR bit 2: this workgroup's state scratch (scalar registers, made where it is used)
+      auto scratch_rsrc = [&]() {
+        return __builtin_amdgcn_make_buffer_rsrc(SCRV ? a.scr + (int64_t)blockIdx.x * ((HS - 1) * (SCR_CH / 2)) : nullptr, 0, SCRV ? (HS - 1) * SCR_CH : 0, 0x00020000);
+      };
       auto request_next_operand = [&]() {
         if (ITEMS || !(last && more)) return;
         // the next step's operand: x_{t+1} (laid out two steps ahead, or by the caller) and the state features of the earlier chunks
@@ -761,7 +779,8 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         const int qo = lane_now() >> 4;
         int sw[STILES];
         slot_words(lane, sw);
-        const __amdgpu_buffer_rsrc_t rsrc_hn = __builtin_amdgcn_make_buffer_rsrc(hout, 0, B * (NP * F * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_hn = __builtin_amdgcn_make_buffer_rsrc(SCRV ? nullptr : hout, 0, SCRV ? 0 : B * (NP * F * 2), 0x00020000);
+        [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsrc_sn = scratch_rsrc();
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
           if (s == HS - 1) continue;
@@ -771,7 +790,9 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 #ifdef GCRNN_SEQ32_EXPERIMENT_SKIP      // timing experiment, WRONG results: 1 = no state requests, 2 = no input requests (which half of the operand costs the wait?)
             if ((GCRNN_SEQ32_EXPERIMENT_SKIP == 1) == (s < HS)) continue;
 #endif
-            if (s < HS)
+            if (SCRV && s < HS)      // this lane's own 16 bytes of the scratch (slot order: no slot word), sc1
+              bfr[i][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_sn, (lane_now() & 15) * 64 + 16 * qo, s * SCR_CH + (wave * STILES + i) * 1024, 16));
+            else if (s < HS)
               bfr[i][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_hn, (w >> 16) * (F * 2) + 16 * qo + 64 * s, b * (NP * F * 2), GCRNN_SEQ32_NT_XLOAD));
             else
               bfr[i][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_xn, (w >> 16) * (G * 2) + 16 * qo + 64 * (s - HS), b * (NP * G * 2), GCRNN_SEQ32_NT_XLOAD));
@@ -960,8 +981,14 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           p[3] = pack2bf(fast_tanh(a1[2] + bs[1][2]), fast_tanh(a1[3] + bs[1][3]));
         }
         pkd[i] = p;
+        if constexpr (SCRV) {
+          // chunks 0 .. HS-2 into the workgroup's scratch at the lane's SLOT (padding slots store their zeros every step: the next step reads
+          // them back); the last chunk's features stay in registers and leave through the user-layout tile only
+          if (!last) __builtin_amdgcn_raw_buffer_store_b128(p, scratch_rsrc(), (lane & 15) * 64 + 16 * q, chunk * SCR_CH + (wave * STILES + i) * 1024, 0);
+        } else
         if (GCRNN_SEQ32_NT_STATE && last) __builtin_amdgcn_raw_buffer_store_b128(p, rsrc_o, node * (F * 2) + (chunk * 32 + q * 8) * 2, b * (NP * F * 2), GCRNN_SEQ32_NT_STATE);
         else __builtin_amdgcn_raw_buffer_store_b128(p, rsrc_o, node * (F * 2) + (chunk * 32 + q * 8) * 2, b * (NP * F * 2), 0);
+        static_assert(!SCRV || GCRNN_SEQ32_OPERAND_AT != 3, "state scratch: the per-tile request form reads the state image");
         if (GCRNN_SEQ32_OPERAND_AT == 3 && last && more) {
           // the next operand's fragments of THIS tile (its registers died with the last tap), a tile at a time between the epilogue's own
           // work: a wave that issues all 24 requests at once sits in their issue for most of the fetch (the memory pipeline takes a request

@@ -224,23 +224,55 @@ static int seq32_launch_pair(const Seq32Args& sa, bool inline_pack, hipStream_t 
 // xs [T][B][NP][G] bf16 sequence-major (every step laid out, or -- with Xuser_inline = the user-layout X [B][T][G][N] -- steps 0 and 1 only:
 // step t lays out x_{t+2}), h0 [B][NP][F], hs [T][B][NP][F] (out), wpack from gcrnn_fused_pack_weights_wide, bias [F] fp32 or NULL,
 // plan arrays of the bf16-image plan; Huser [B][T or 1][F][N] bf16 or NULL (huser_last_only: the last step only).
-extern "C" int gcrnn_fused_forward_wide_bf16(const void* xs, const void* h0, void* hs, const void* wpack, const float* bias,
-                                             const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4, int64_t entries,
-                                             int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, void* Huser,
-                                             int huser_last_only, const void* Xuser_inline, const float* rank1_a, const float* rank1_b,
-                                             void* stream) {
-  if (!xs || !h0 || !hs || !wpack || !tile_nodes || !tile_off || !ell_col4) return GCRNN_ERR_NULL_POINTER;
+//
+// Inference without a state image (gcrnn_fused_forward_wide_scratch_bf16: the same arguments with hs replaced by `scratch` and its size in
+// bytes): with the user-layout output nobody reads hs, and the launch itself re-reads only the chunks 0 .. F/32-2 of h_t one step later. Those
+// go to `scratch` ([workgroups][F/32-1][NPad][32] bf16 in slot order, gcrnn_fused_seq32.h VAR bit 2; contents undefined before and after, never
+// to be shared by two launches that may run at once); the last chunk is handed over in registers and not stored. Huser is required.
+// gcrnn_fused_forward_wide_scratch_bytes: the bytes `scratch` needs (0 at F = 32: it may then be NULL), or -1 when this form does not take
+// the problem and the caller keeps gcrnn_fused_forward_wide_bf16 -- a split batch (one launch per step: the launch boundary is the hand-over),
+// GCRNN_SEQ32P=1 (the hand-allocated hop has no such variant) or GCRNN_SEQ32_STATE_SCRATCH=0 (same-binary A/B and the bit-identity tests).
+int gcrnn_seq32s_forward(const Seq32Args& sa, int K, int HS, int XS, bool inline_pack, size_t lds, hipStream_t st);
+
+static int64_t seq32_scratch_need(int64_t B, int64_t F) {
+  const int64_t wgs = B < gcrnn_persistent_grid() ? B : gcrnn_persistent_grid();
+  return wgs * (F / 32 - 1) * (int64_t)NP * 64;
+}
+
+extern "C" int64_t gcrnn_fused_forward_wide_scratch_bytes(int64_t B, int64_t F, int rank1) {
+  if (B <= 0 || F <= 0 || F % 32) return -1;
+  const char* sw = getenv("GCRNN_SEQ32_STATE_SCRATCH");
+  if (sw && sw[0] == '0') return -1;
+  const char* p32 = getenv("GCRNN_SEQ32P");
+  if (p32 && p32[0] != '0') return -1;
+  if (!rank1 && !seq32_wanted(B) && seq32_split_wanted(B, F)) return -1;
+  return seq32_scratch_need(B, F);
+}
+
+static int forward_wide_impl(const void* xs, const void* h0, void* hs, void* scratch, int64_t scratch_bytes, bool no_image, const void* wpack, const float* bias,
+                             const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4, int64_t entries,
+                             int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, void* Huser,
+                             int huser_last_only, const void* Xuser_inline, const float* rank1_a, const float* rank1_b,
+                             void* stream) {
+  if (!xs || !h0 || (!no_image && !hs) || !wpack || !tile_nodes || !tile_off || !ell_col4) return GCRNN_ERR_NULL_POINTER;
+  if (no_image && !Huser) return GCRNN_ERR_NULL_POINTER;
   if ((rank1_a == nullptr) != (rank1_b == nullptr)) return GCRNN_ERR_BAD_SHAPE;
   if ((gi == nullptr) != (gf == nullptr) || (gi && Xuser_inline)) return GCRNN_ERR_BAD_SHAPE;
   if (B <= 0 || T <= 0 || N <= 0 || N > NP || B > (1 << 24) || entries <= 0 || entries % 4) return GCRNN_ERR_BAD_SHAPE;
   if (B * (NP * (F > G ? F : G) * 2) > 2147483647LL || T * F * N > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;   // 32-bit buffer offsets
   if (Huser && (N % 8 != 0 || (reinterpret_cast<uintptr_t>(Huser) & 15))) return GCRNN_ERR_BAD_SHAPE;
   if (Xuser_inline && (N % 8 != 0 || (reinterpret_cast<uintptr_t>(Xuser_inline) & 15) || T * G * N > 2147483647LL)) return GCRNN_ERR_BAD_SHAPE;
+  if (no_image) {      // (checked before anything is launched)
+    if (F % 32 || F < 32) return GCRNN_ERR_UNSUPPORTED;
+    const int64_t need = seq32_scratch_need(B, F);
+    if (scratch_bytes < need || (need > 0 && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15)))) return GCRNN_ERR_BAD_SHAPE;
+  }
   const int64_t xstep = B * NP * G, hstep = B * NP * F;
   Seq32Args sa{};
   sa.x0 = (const uint16_t*)xs; sa.xstride = xstep;
   sa.hfirst = (const uint16_t*)h0;
-  sa.out0 = (uint16_t*)hs; sa.ostride = hstep;
+  sa.out0 = no_image ? nullptr : (uint16_t*)hs; sa.ostride = hstep;
+  sa.scr = no_image ? (uint16_t*)scratch : nullptr;
   sa.wpack = (const uint4*)wpack; sa.bias = bias;
   sa.a1 = (const uint16_t*)Huser; sa.a1stride = F * N; sa.a1_last_only = huser_last_only ? 1 : 0;
   sa.ubstride = (int)((huser_last_only ? 1 : T) * F * N);
@@ -263,6 +295,19 @@ extern "C" int gcrnn_fused_forward_wide_bf16(const void* xs, const void* h0, voi
   hipStream_t st = as_stream(stream);
   // split sequences: the plain un-gated forward of a batch that would leave half of the chip idle (and is not forced onto the persistent form)
   const bool split = !rank1_a && !seq32_wanted(B) && seq32_split_wanted(B, F);
+  if (no_image) {      // the persistent form only (a split batch hands h_t over between launches)
+    if (split) return GCRNN_ERR_UNSUPPORTED;
+#define GCRNN_SEQ32_CASE(KK, HH, XX) \
+    if (K == KK && F == 32 * HH && G == 32 * XX) { \
+      const size_t lds = seq32_lds<KK, HH, XX>(sa.entries, inline_pack, sa.r1a != nullptr); \
+      return lds ? gcrnn_seq32s_forward(sa, KK, HH, XX, inline_pack, lds, st) : GCRNN_ERR_UNSUPPORTED; \
+    }
+    GCRNN_SEQ32_CASE(5, 2, 2) GCRNN_SEQ32_CASE(4, 2, 2) GCRNN_SEQ32_CASE(3, 2, 2) GCRNN_SEQ32_CASE(2, 2, 2)
+    GCRNN_SEQ32_CASE(5, 2, 1) GCRNN_SEQ32_CASE(4, 2, 1) GCRNN_SEQ32_CASE(3, 2, 1) GCRNN_SEQ32_CASE(2, 2, 1)
+    GCRNN_SEQ32_CASE(5, 1, 1) GCRNN_SEQ32_CASE(4, 1, 1) GCRNN_SEQ32_CASE(3, 1, 1) GCRNN_SEQ32_CASE(2, 1, 1)
+#undef GCRNN_SEQ32_CASE
+    return GCRNN_ERR_UNSUPPORTED;
+  }
   const bool pack_split = Xuser_inline != nullptr && T > 1;      // (one launch per step: launch t lays out x_{t+1}; the caller laid out x_0)
   if (split && pack_split && !inline_pack) {
     sa.pk_src0 = (const uint16_t*)Xuser_inline; sa.pksrc_stride = G * N;
@@ -275,6 +320,24 @@ extern "C" int gcrnn_fused_forward_wide_bf16(const void* xs, const void* h0, voi
   GCRNN_SEQ32_CASE(5, 1, 1) GCRNN_SEQ32_CASE(4, 1, 1) GCRNN_SEQ32_CASE(3, 1, 1) GCRNN_SEQ32_CASE(2, 1, 1)
 #undef GCRNN_SEQ32_CASE
   return GCRNN_ERR_UNSUPPORTED;
+}
+
+extern "C" int gcrnn_fused_forward_wide_bf16(const void* xs, const void* h0, void* hs, const void* wpack, const float* bias,
+                                             const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4, int64_t entries,
+                                             int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, void* Huser,
+                                             int huser_last_only, const void* Xuser_inline, const float* rank1_a, const float* rank1_b,
+                                             void* stream) {
+  return forward_wide_impl(xs, h0, hs, nullptr, 0, false, wpack, bias, gi, gf, tile_nodes, tile_off, ell_col4, entries, B, T, N, F, G, K, Huser,
+                           huser_last_only, Xuser_inline, rank1_a, rank1_b, stream);
+}
+
+extern "C" int gcrnn_fused_forward_wide_scratch_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack, const float* bias,
+                                                     const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4,
+                                                     int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, void* Huser,
+                                                     int huser_last_only, const void* Xuser_inline, const float* rank1_a, const float* rank1_b,
+                                                     void* stream) {
+  return forward_wide_impl(xs, h0, nullptr, scratch, scratch_bytes, true, wpack, bias, gi, gf, tile_nodes, tile_off, ell_col4, entries, B, T, N, F, G, K, Huser,
+                           huser_last_only, Xuser_inline, rank1_a, rank1_b, stream);
 }
 
 

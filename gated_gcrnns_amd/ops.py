@@ -387,10 +387,11 @@ def time_fused_step_kernel(X, h0, wA, wB, bias, graph, reps=3, inline=None, user
     if wide is not None:
         # the wide sequence-resident kernel (what fused_cell_forward issues for this problem): ONE launch per forward
         wpw = _fused_pack_weights_wide(wAc, wBc, wide['uniform_w'], st)
+        scr = fused_state_scratch(wide, B, F, dev) if H is not None else None      # the launch the module issues under no_grad: no state image
         for rep in range(reps + warm):
             if rep == warm:
                 e0.record()                              # (no synchronisation here: the timed launches follow the warm ones without an idle gap)
-            _fused_forward_wide(wide, xs, h0s, hs, wAc, wBc, b32, B, T, N, F, G, K, H, False, Xc if inline else None, st, wpw=wpw)
+            _fused_forward_wide(wide, xs, h0s, hs, wAc, wBc, b32, B, T, N, F, G, K, H, False, Xc if inline else None, st, wpw=wpw, scratch=scr)
         e1.record()
         torch.cuda.synchronize()
         per_step = 1e3 * e0.elapsed_time(e1) / (reps * T)
@@ -531,9 +532,28 @@ def fused_wide_plan(graph, B, T, N, F, G, K, inline, rank1=False, gated=False):
     return plan16 if ok else None
 
 
-def _fused_forward_wide(plan16, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H, last_only, Xinline, st, wpw=None, gi=None, gf=None):
+def fused_state_scratch(plan16, B, F, dev):
+    """The scratch of the wide forward WITHOUT a state image (gcrnn_fused_forward_wide_scratch_bf16: inference through the user-layout H -- the
+    launch keeps only what it re-reads itself, chunks 0 .. F/32-2 of h_t in slot order, 64 KB per workgroup at F = 64), or None when that form
+    does not take the problem (split batch, GCRNN_SEQ32_STATE_SCRATCH=0, GCRNN_SEQ32P=1: the caller passes hs). Allocated per forward on the
+    current stream, like hs: two forwards on two streams never share one."""
+    need = int(lib.gcrnn_fused_forward_wide_scratch_bytes(int(B), int(F), 1 if plan16.get('rank1') else 0))
+    if need < 0:
+        return None
+    return torch.empty((need,), dtype=torch.uint8, device=dev)
+
+
+def _fused_forward_wide(plan16, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H, last_only, Xinline, st, wpw=None, gi=None, gf=None, scratch=None):
     if wpw is None:
         wpw = _fused_pack_weights_wide(wA.detach(), wB.detach(), plan16['uniform_w'], st)
+    if scratch is not None:                              # no state image: hs is not touched (and need not exist)
+        assert H is not None
+        check(lib.gcrnn_fused_forward_wide_scratch_bf16(_p(xs), _p(h0s), _p(scratch), int(scratch.numel()), _p(wpw), _p(b32), _p(gi), _p(gf), _p(plan16['tile_slots']),
+                                                        _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries'], B, T, N, F, G, K,
+                                                        _p(H), int(bool(last_only)), _p(Xinline) if Xinline is not None else None,
+                                                        _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
+              'fused_forward_wide_scratch')
+        return
     check(lib.gcrnn_fused_forward_wide_bf16(_p(xs), _p(h0s), _p(hs), _p(wpw), _p(b32), _p(gi), _p(gf), _p(plan16['tile_slots']), _p(plan16['tile_off']),
                                             _p(plan16['ell_col4']), plan16['entries'], B, T, N, F, G, K,
                                             _p(H) if H is not None else None, int(bool(last_only)), _p(Xinline) if Xinline is not None else None,
@@ -580,28 +600,31 @@ def fused_pad_taps(wA):
     return wA if Gp == G else torch.nn.functional.pad(wA, (0, Gp - G))
 
 
-def fused_pack_inputs(X, h0, graph, overlap=False, first_only=False, channels=None):
+def fused_pack_inputs(X, h0, graph, overlap=False, first_only=False, channels=None, states=True):
     """user-layout bf16 X [B][T][G][N], h0 [B][F][N] -> sequence-major xs [T][B][NPad][G] and the state buffer
     hs_all [T+1][B][NPad][F] whose slot 0 holds h0 (slots 1..T receive h_1..h_T: hs_all[:T] is then the h_{t-1} operand of
     every step, which the gate-gradient pass reads as one array).
     overlap: only step 0 is packed on the current stream; every later step is packed on a side stream by a kernel small
     enough (4 KiB of LDS, bounded grid) to run beside the step kernels, each followed by an event. Returns (xs, hs_all,
-    events) with events[t] = the event step t's launch has to wait for -- the recurrence starts after 1/T of the pack."""
+    events) with events[t] = the event step t's launch has to wait for -- the recurrence starts after 1/T of the pack.
+    states=False: hs_all is slot 0 alone (inference that may run without a state image, fused_state_scratch; a caller that turns out to
+    need the image allocates it then)."""
     B, T, G, N = X.shape
     F = h0.shape[1]
     npad = graph.fused_plan()['npad']
     st = _stream()
+    TS = T if states else 0
     Xc, h0c = X.contiguous(), h0.contiguous()
     if channels is not None and channels != G:
         # X keeps its own G channels in the user layout; the sequence-major array gets `channels` of them, the rest zeros
         assert channels > G and not overlap and not first_only
         xs = torch.empty((T, B, npad, channels), dtype=torch.bfloat16, device=X.device)
-        hs_all = torch.empty((T + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
+        hs_all = torch.empty((TS + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
         check(lib.gcrnn_pack_seq_major(_lib.BF16, _p(h0c), _p(hs_all), B, 1, F, N, npad, None, st), 'pack_seq')
         check(lib.gcrnn_pack_seq_major_padded(_p(Xc), _p(xs), B, T, G, channels, N, npad, st), 'pack_seq_padded')
         return xs, hs_all
     xs = torch.empty((T, B, npad, G), dtype=torch.bfloat16, device=X.device)
-    hs_all = torch.empty((T + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
+    hs_all = torch.empty((TS + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
     check(lib.gcrnn_pack_seq_major(_lib.BF16, _p(h0c), _p(hs_all), B, 1, F, N, npad, None, st), 'pack_seq')
     if first_only:                                       # x_0 and x_1 only: the step kernels lay out every later step themselves (inline pack;
         # the sequence-resident kernel works two steps ahead, the chunk-parallel one re-writes x_1 with the same bits)
@@ -632,7 +655,7 @@ def fused_pack_inputs(X, h0, graph, overlap=False, first_only=False, channels=No
     return xs, hs_all, events
 
 
-def fused_pack_inputs_gated(X, h0, graph, F, K):
+def fused_pack_inputs_gated(X, h0, graph, F, K, states=True):
     """fused_pack_inputs for a cell whose FIRST consumer of xs is a gate pre-pass (fused_time_gate): on a uniform-weight graph with
     a batch that fills the chip, only the first time step(s) are laid out here and that pre-pass lays out the rest while it runs
     (gcrnn_fused_gate_prepass_pack_bf16: every item packs the operand of its workgroup's next item) -- the 0.5 ms pass over X at
@@ -646,11 +669,11 @@ def fused_pack_inputs_gated(X, h0, graph, F, K):
         if steps <= 0:
             steps = int(lib.gcrnn_fused_gate_prepass_lays_out(B, T, N, F, G, K, plan16['entries'], plan.get('uniform_w', 0.0), 1))
     if steps <= 0 or steps >= T:
-        return fused_pack_inputs(X, h0, graph)
+        return fused_pack_inputs(X, h0, graph, states=states)
     npad = plan['npad']
     st = _stream()
     xs = torch.empty((T, B, npad, G), dtype=torch.bfloat16, device=X.device)
-    hs_all = torch.empty((T + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
+    hs_all = torch.empty(((T if states else 0) + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
     check(lib.gcrnn_pack_seq_major(_lib.BF16, _p(h0.contiguous()), _p(hs_all), B, 1, F, N, npad, None, st), 'pack_seq')
     check(lib.gcrnn_pack_seq_major_steps(_p(X), _p(xs), B, T, G, N, npad, 0, steps, 0, st), 'pack_seq_steps')
     xs._pending_user = X
@@ -830,6 +853,9 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     h0 = h0.contiguous()
     events = None
     inline = False
+    # inference through the user-layout H: the wide kernel then runs without a state image (fused_state_scratch) and hs is not allocated
+    # here; a path that does need it allocates it below
+    lean = packed is None and head is None and not return_states and not native_out and N % 8 == 0
     if packed is not None:
         xs, hs_all = packed
     elif gates is None and gate_values is None and X.data_ptr() % 16 == 0 and (
@@ -837,14 +863,14 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
                                                        and fused_wide_plan(graph, B, T, N, F, G, K, True, rank1=True) is not None)):
         # un-gated cell on a uniform-weight graph: only x_0 is packed here, launch t lays out x_{t+1} itself (LDS-DMA into the room
         # the missing weight image leaves, read back transposed after the epilogue) -- no pack pass over X
-        xs, hs_all = fused_pack_inputs(X, h0, graph, first_only=True)
+        xs, hs_all = fused_pack_inputs(X, h0, graph, first_only=True, states=not lean)
         inline = True
     elif gates is None and fused_overlap_ok(X):          # (the gate pre-passes read every x_t at once: nothing to hide behind)
-        xs, hs_all, events = fused_pack_inputs(X, h0, graph, overlap=True)
+        xs, hs_all, events = fused_pack_inputs(X, h0, graph, overlap=True, states=not lean)
     elif gates is not None and gate_values is None:
-        xs, hs_all = fused_pack_inputs_gated(X, h0, graph, F, K)       # (the first gate pre-pass lays out x_1 .. x_{T-1})
+        xs, hs_all = fused_pack_inputs_gated(X, h0, graph, F, K, states=not lean)       # (the first gate pre-pass lays out x_1 .. x_{T-1})
     else:
-        xs, hs_all = fused_pack_inputs(X, h0, graph)
+        xs, hs_all = fused_pack_inputs(X, h0, graph, states=not lean)
     h0s, hs = hs_all[:1], hs_all[1:]
     gi = gf = None
     if gate_values is not None:
@@ -896,13 +922,18 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
             Hv = hs.permute(1, 0, 3, 2)[:, :, :, :N]
             return Hv[:, T - 1:] if last_only else Hv
         H = torch.empty((B, 1 if last_only else T, F, N), dtype=torch.bfloat16, device=dev)
-        _fused_forward_wide(wide, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H if direct else None, last_only, X if inline else None, st, gi=gi, gf=gf)
+        scr = fused_state_scratch(wide, B, F, dev) if (direct and not return_states) else None
+        if scr is None and hs.shape[0] == 0:
+            hs = torch.empty((T,) + tuple(h0s.shape[1:]), dtype=torch.bfloat16, device=dev)
+        _fused_forward_wide(wide, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H if direct else None, last_only, X if inline else None, st, gi=gi, gf=gf, scratch=scr)
         if not direct:
             src = hs[T - 1:] if last_only else hs
             check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(src), _p(H), B, 1 if last_only else T, F, N, plan['npad'], None, st), 'unpack_seq')
         if return_states:
             return hs_all, plan, H
         return H
+    if hs.shape[0] == 0:                                 # (lean, and not the wide kernel after all: the step kernels keep the state image)
+        hs = torch.empty((T,) + tuple(h0s.shape[1:]), dtype=torch.bfloat16, device=dev)
     plan16 = fused_img16_plan(graph, gi is not None, None)
     wpack = _fused_pack_weights(wA, wB, st)
     if native_out:

@@ -436,6 +436,14 @@ int gcrnn_fused_forward_bf16(const void* xs, const void* h0, void* hs, const voi
  *   reads it ends --, h0 [B][NPad][F], hs [T][B][NPad][F] (out), bias [F] fp32 or NULL (added by both filters, graphML.py:2420-2421),
  *   gi / gf: NULL, or the scalar time gates [T][B] fp32 (graphML.py:2357-2374), tile_nodes / tile_off / ell_col4 = the bf16-image plan
  *   (graph.fused_plan_img16), Huser [B][T][F][N] bf16 or NULL (huser_last_only: [B][1][F][N], the last state only).
+ * gcrnn_fused_forward_wide_scratch_bf16: the same forward WITHOUT the state image, for inference through Huser (required): `hs` is replaced
+ *   by `scratch` and its size in bytes. The launch re-reads only the chunks 0 .. F/32-2 of h_t, one step later; they live in `scratch`
+ *   ([workgroups][F/32-1][NPad][32] bf16 in the kernel's slot order -- contents undefined before and after the call, not to be shared by
+ *   launches that may run at once), the last chunk is handed over in registers and never stored. H is bit-identical to
+ *   gcrnn_fused_forward_wide_bf16's. GCRNN_ERR_BAD_SHAPE (nothing launched) when scratch_bytes is too small.
+ * gcrnn_fused_forward_wide_scratch_bytes: the bytes that scratch needs (0 at F = 32: it may then be NULL), or -1 when that form does not
+ *   take the problem and the caller keeps gcrnn_fused_forward_wide_bf16: a batch that runs as split sequences (rank1 = 0 only), or
+ *   GCRNN_SEQ32_STATE_SCRATCH=0 / GCRNN_SEQ32P=1 in the environment (same-binary A/B).
  * gcrnn_fused_gate_pair_wide_supported: 0, or -- with_pack -- the number of leading time steps of xs the caller lays out itself (1 without).
  * gcrnn_fused_gate_pair_prepass_wide_bf16: both time gates of every (t, b) in one launch; wpack = gcrnn_fused_pack_weights_wide(Fout = 2 F) of
  *   [GFL_in ; GFL_forget] stacked over the output features, bias2 [2 F], gw2 [2][N][F] fp32 = the read-outs' weights node-major, parts
@@ -455,6 +463,12 @@ int gcrnn_fused_forward_wide_bf16(const void* xs, const void* h0, void* hs, cons
                                      S[m][n] = a[m] b[n] (normalised adjacencies, Utils/graphTools.py:64) -- the two factors [NPad] fp32 (zero for
                                      padding rows); the plan arrays are then those of the graph's 0/1 pattern and wpack carries uniform_w = 1 */,
                                   void* stream);
+int64_t gcrnn_fused_forward_wide_scratch_bytes(int64_t B, int64_t F, int rank1);
+int gcrnn_fused_forward_wide_scratch_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack,
+                                          const float* bias, const float* gi, const float* gf, const int32_t* tile_nodes,
+                                          const int32_t* tile_off, const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N,
+                                          int64_t F, int64_t G, int64_t K, void* Huser, int huser_last_only, const void* Xuser_inline,
+                                          const float* rank1_a, const float* rank1_b, void* stream);
 int gcrnn_fused_gate_pair_wide_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries, double uniform_w,
                                          int img16, int with_pack);
 /* The BPTT data chain as ONE launch of the wide kernel: gcrnn_fused_backward_data_bf16's contract (seed included), with wpackT =

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Run only the fused step kernel chain (no pack/unpack) for profiling: python3 tools/step_kernel_probe.py [B] [T] [reps]"""
+"""Run only the fused step kernel chain (no pack/unpack) for profiling: python3 tools/step_kernel_probe.py [B] [T] [reps] [native|infer]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -32,6 +32,18 @@ if NATIVE:
             cell.forward_native(xs, None)
         torch.cuda.synchronize()
     print('per step (native layout): %.1f us' % (1e6 * (time.perf_counter() - t0) / reps / T))
+    sys.exit(0)
+INFER = len(sys.argv) > 4 and sys.argv[4] == 'infer'        # the forward as the module issues it under no_grad: no state image (state scratch)
+if INFER:
+    with torch.no_grad():
+        for _ in range(reps):
+            ops.fused_cell_forward(X, h0, cell.weight_A, cell.weight_B, cell.bias, cell.graph)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            ops.fused_cell_forward(X, h0, cell.weight_A, cell.weight_B, cell.bias, cell.graph)
+        torch.cuda.synchronize()
+    print('per step (inference, incl. pack of x): %.1f us' % (1e6 * (time.perf_counter() - t0) / reps / T))
     sys.exit(0)
 with torch.no_grad():
     for _ in range(reps):
