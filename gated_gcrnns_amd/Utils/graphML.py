@@ -600,21 +600,36 @@ class GGCRNNCell(nn.Module):
         return self.spatial_gating == 'node' and \
             ops.small_dense_supported(self.N, self.G, self.F, self.Kin, self.Kst, X.dtype, backward=backward, gated=True)
 
+    # -- conditions the _use_* questions below share ----
+    def _sigma_is_tanh(self):
+        return self.sigma in (torch.tanh, nn.functional.tanh)
+
+    def _all_fp32(self, X, h0):
+        return X.dtype == torch.float32 and h0.dtype == X.dtype and self.weight_A.dtype == X.dtype
+
+    def _small_takes(self, X):
+        """The one-launch small-graph kernels take this cell's shapes (the fp32-accurate fused paths leave those to them)."""
+        return ops.small_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E)
+
+    def _attention_fusable(self):
+        """The edge gates' attention is the one the fused attention kernels evaluate: one head, one edge feature, concatenated, relu."""
+        att = self.input_attention
+        return att.K == 1 and att.E == 1 and att.concatenate and att.nonlinearity is nn.functional.relu
+
     def _use_small(self, X, h0):
         if self._wants_grad(X, h0):
             return False
-        if self.sigma not in (torch.tanh, nn.functional.tanh):
+        if not self._sigma_is_tanh():
             return False
         if self.spatial_gating is not None and not self._small_node_gating_ok(X, False):
             return False
-        return self.weight_A.dtype == X.dtype and h0.dtype == X.dtype and \
-            ops.small_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E)
+        return self.weight_A.dtype == X.dtype and h0.dtype == X.dtype and self._small_takes(X)
 
     def _use_small_training(self, X, h0):
         """Small graphs, gradients wanted for parameters / h0 but not for X: forward and BPTT are one launch each."""
         if not torch.is_grad_enabled() or X.requires_grad:
             return False
-        if self.sigma not in (torch.tanh, nn.functional.tanh):
+        if not self._sigma_is_tanh():
             return False
         if self.spatial_gating is not None and not self._small_node_gating_ok(X, True):
             return False
@@ -658,7 +673,7 @@ class GGCRNNCell(nn.Module):
     def _use_fused(self, X, h0):
         if self._wants_grad(X, h0):
             return False            # BPTT runs on the fused training path or the composed path
-        if self.spatial_gating is not None or self.sigma not in (torch.tanh, nn.functional.tanh):
+        if self.spatial_gating is not None or not self._sigma_is_tanh():
             return False
         return ops.fused_supported(self.N, self.F, self.G, self.Kin, self.Kst, X.dtype, self.E) and \
             self.weight_A.dtype in (X.dtype, torch.float32) and h0.dtype == X.dtype
@@ -666,7 +681,7 @@ class GGCRNNCell(nn.Module):
     def _use_fused_node(self, X, h0):
         """Node-gated cell (optionally time-gated too), bf16, inference: fused kernels (gates, A(S)x_t + b and both gate filters for
         all steps at once; the recurrence on the state-only operand with per-node gates in its epilogue)."""
-        if self._wants_grad(X, h0) or self.spatial_gating != 'node' or self.sigma not in (torch.tanh, nn.functional.tanh):
+        if self._wants_grad(X, h0) or self.spatial_gating != 'node' or not self._sigma_is_tanh():
             return False
         if self.bias is None and self.time_gating == True:  # noqa: E712
             return False
@@ -690,12 +705,11 @@ class GGCRNNCell(nn.Module):
     def _use_fused_edge(self, X, h0):
         """Edge-gated cell (optionally time-gated too), bf16, inference: the attention's mixing matrix is folded into the filter taps,
         the x branch runs for all steps at once, every step is a filter pass plus the attention kernel."""
-        if self._wants_grad(X, h0) or self.spatial_gating != 'edge' or self.sigma not in (torch.tanh, nn.functional.tanh):
+        if self._wants_grad(X, h0) or self.spatial_gating != 'edge' or not self._sigma_is_tanh():
             return False
         if self.bias is None and self.time_gating == True:  # noqa: E712
             return False
-        att = self.input_attention
-        if att.K != 1 or att.E != 1 or not att.concatenate or att.nonlinearity is not nn.functional.relu:
+        if not self._attention_fusable():
             return False
         return ops.fused_edge_supported(self.graph, self.N, self.F, self.G, self.Kin, self.Kst, X.dtype, self.E) and \
             self.weight_A.dtype in (X.dtype, torch.float32) and h0.dtype == X.dtype
@@ -712,35 +726,35 @@ class GGCRNNCell(nn.Module):
         question for the time-gated cell (ops.fused_cell_forward_x3_gated: gates and scaled steps composed from the same kernel)."""
         if self._wants_grad(X, h0):
             return False
-        if (self.time_gating == True) != bool(time_gated) or self.spatial_gating is not None or self.sigma not in (torch.tanh, nn.functional.tanh):  # noqa: E712
+        if (self.time_gating == True) != bool(time_gated) or self.spatial_gating is not None or not self._sigma_is_tanh():  # noqa: E712
             return False
         if time_gated and (X.shape[0] > 2048 or os.environ.get('GCRNN_NO_X3_GATED')):
             return False
-        if X.dtype != torch.float32 or h0.dtype != X.dtype or self.weight_A.dtype != X.dtype:
+        if not self._all_fp32(X, h0):
             return False
-        if ops.small_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E):
+        if self._small_takes(X):
             return False
         return ops.fused_x3_supported(self.graph, self.N, self.F, self.G, self.Kin, self.Kst, X.dtype, self.E, X.shape[0], X.shape[1])
 
     def _use_fused_x3_node(self, X, h0):
         """fp32 inference of the NODE-gated cell (with or without time gates) on the fp32-accurate fused kernels (round 5,
         ops.fused_node_cell_forward_x3): the x3 conditions with G == F."""
-        if self._wants_grad(X, h0) or self.spatial_gating != 'node' or self.sigma not in (torch.tanh, nn.functional.tanh):
+        if self._wants_grad(X, h0) or self.spatial_gating != 'node' or not self._sigma_is_tanh():
             return False
-        if X.dtype != torch.float32 or h0.dtype != X.dtype or self.weight_A.dtype != X.dtype or X.shape[0] > 2048:
+        if not self._all_fp32(X, h0) or X.shape[0] > 2048:
             return False
-        if ops.small_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E):
+        if self._small_takes(X):
             return False
         return ops.fused_node_x3_supported(self.graph, self.N, self.F, self.G, self.Kin, self.Kst, X.dtype, self.E, X.shape[0], X.shape[1])
 
     def _use_fused_x3_edge(self, X, h0):
         """fp32 inference of the EDGE-gated cell (with or without time gates) with both filters on the fp32-accurate fused kernels (round 5,
         ops.fused_edge_cell_forward_x3; the attentions run on the fp32 CSR edge-softmax kernels): the x3 conditions with G == F."""
-        if self._wants_grad(X, h0) or self.spatial_gating != 'edge' or self.sigma not in (torch.tanh, nn.functional.tanh):
+        if self._wants_grad(X, h0) or self.spatial_gating != 'edge' or not self._sigma_is_tanh():
             return False
-        if X.dtype != torch.float32 or h0.dtype != X.dtype or self.weight_A.dtype != X.dtype or X.shape[0] > 2048 or os.environ.get('GCRNN_NO_X3_EDGE'):
+        if not self._all_fp32(X, h0) or X.shape[0] > 2048 or os.environ.get('GCRNN_NO_X3_EDGE'):
             return False
-        if ops.small_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E):
+        if self._small_takes(X):
             return False
         return self.G == self.F and ops.fused_x3_supported(self.graph, self.N, self.F, self.G, self.Kin, self.Kst, X.dtype, self.E, X.shape[0], X.shape[1])
 
@@ -753,11 +767,11 @@ class GGCRNNCell(nn.Module):
             return False
         if not (h0.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
-        if (self.time_gating == True) != bool(time_gated) or self.spatial_gating is not None or self.sigma not in (torch.tanh, nn.functional.tanh):  # noqa: E712
+        if (self.time_gating == True) != bool(time_gated) or self.spatial_gating is not None or not self._sigma_is_tanh():  # noqa: E712
             return False
-        if X.dtype != torch.float32 or h0.dtype != X.dtype or self.weight_A.dtype != X.dtype or os.environ.get('GCRNN_NO_X3_TRAINING'):
+        if not self._all_fp32(X, h0) or os.environ.get('GCRNN_NO_X3_TRAINING'):
             return False
-        if ops.small_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E):
+        if self._small_takes(X):
             return False
         if time_gated:
             if h0.requires_grad or self.GFL_in.weight_A.dtype != X.dtype or os.environ.get('GCRNN_NO_X3_GATED'):
@@ -779,9 +793,7 @@ class GGCRNNCell(nn.Module):
                     not ops.fused_node_supported(self.graph, self.N, self.F, self.G, self.Kin, self.Kst, X.dtype, self.E):
                 return False
         elif self.spatial_gating == 'edge':
-            att = self.input_attention
-            if h0.requires_grad or att.K != 1 or att.E != 1 or not att.concatenate or att.nonlinearity is not nn.functional.relu or \
-                    att.weight.dtype != self.weight_A.dtype or \
+            if h0.requires_grad or not self._attention_fusable() or self.input_attention.weight.dtype != self.weight_A.dtype or \
                     not ops.fused_edge_training_supported(self.graph, self.N, self.F, self.G, self.Kin, self.Kst, self.E):
                 return False
         elif self.spatial_gating is not None:
@@ -789,7 +801,7 @@ class GGCRNNCell(nn.Module):
         if self.time_gating == True:  # noqa: E712   the gates' sub-cells share the cell's shapes; (r4) they hand h0 its gradient when G == F
             if (h0.requires_grad and not ops.fused_input_grad_ok(self.F, self.G)) or self.bias is None or self.GFL_in.weight_A.dtype != self.weight_A.dtype:
                 return False
-        if self.sigma not in (torch.tanh, nn.functional.tanh) or X.dtype != torch.bfloat16 or h0.dtype != X.dtype:
+        if not self._sigma_is_tanh() or X.dtype != torch.bfloat16 or h0.dtype != X.dtype:
             return False
         if self.weight_A.dtype not in (torch.bfloat16, torch.float32):
             return False

@@ -522,9 +522,9 @@ def _fused_pack_weights_wide(wA, wB, uniform_w, st):
 def fused_wide_plan(graph, B, T, N, F, G, K, inline, rank1=False, gated=False):
     """The bf16-image plan when the wide sequence-resident kernel (gcrnn_fused_forward_wide_bf16: un-gated forward as ONE launch, 32-feature
     chunks) takes this problem, else None. GCRNN_SEQ32=0 switches it off (A/B)."""
-    plan16 = fused_img16_plan(graph, False, None)
-    if plan16 is None and rank1 and not os.environ.get('GCRNN_NO_IMG16'):
-        plan16 = graph.fused_plan_rank1()                # rank-1-weighted graph (normalised adjacency): the plan of its 0/1 pattern + the two factor tables
+    plan16 = _forward_plan16(graph)
+    if plan16 is None and rank1:
+        plan16 = _forward_plan16(graph, rank1=True)
     if plan16 is None or F % 32 or G % 32:
         return None
     ok = lib.gcrnn_fused_forward_wide_supported(int(B), int(T), int(N), int(F), int(G), int(K), int(plan16['entries']),
@@ -548,31 +548,58 @@ def _fused_forward_wide(plan16, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H, l
         wpw = _fused_pack_weights_wide(wA.detach(), wB.detach(), plan16['uniform_w'], st)
     if scratch is not None:                              # no state image: hs is not touched (and need not exist)
         assert H is not None
-        check(lib.gcrnn_fused_forward_wide_scratch_bf16(_p(xs), _p(h0s), _p(scratch), int(scratch.numel()), _p(wpw), _p(b32), _p(gi), _p(gf), _p(plan16['tile_slots']),
-                                                        _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries'], B, T, N, F, G, K,
+        check(lib.gcrnn_fused_forward_wide_scratch_bf16(_p(xs), _p(h0s), _p(scratch), int(scratch.numel()), _p(wpw), _p(b32), _p(gi), _p(gf),
+                                                        *_wide_graph_args(plan16), B, T, N, F, G, K,
                                                         _p(H), int(bool(last_only)), _p(Xinline) if Xinline is not None else None,
                                                         _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
               'fused_forward_wide_scratch')
         return
-    check(lib.gcrnn_fused_forward_wide_bf16(_p(xs), _p(h0s), _p(hs), _p(wpw), _p(b32), _p(gi), _p(gf), _p(plan16['tile_slots']), _p(plan16['tile_off']),
-                                            _p(plan16['ell_col4']), plan16['entries'], B, T, N, F, G, K,
+    check(lib.gcrnn_fused_forward_wide_bf16(_p(xs), _p(h0s), _p(hs), _p(wpw), _p(b32), _p(gi), _p(gf),
+                                            *_wide_graph_args(plan16), B, T, N, F, G, K,
                                             _p(H) if H is not None else None, int(bool(last_only)), _p(Xinline) if Xinline is not None else None,
                                             _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
           'fused_forward_wide')
 
 
-def fused_img16_plan(graph, gated, head):
-    """The bf16-image plan of the un-gated forward steps (GraphOperator.fused_plan_img16), or None: uniform-weight graphs only
-    (un-gated and time-gated cells, with or without the fused head); GCRNN_NO_IMG16=1 switches it off (A/B, and the fp32-image tests)."""
-    import os
+def _forward_plan16(graph, rank1=False):
+    """The bf16-image plan of the forward graph (GraphOperator.fused_plan_img16: uniform-weight graphs only) or, with rank1, the plan of a
+    rank-1-weighted graph (normalised adjacency): the plan of its 0/1 pattern + the two factor tables. None where the graph has no such
+    plan; GCRNN_NO_IMG16=1 switches both off (A/B, and the fp32-image tests)."""
     if os.environ.get('GCRNN_NO_IMG16'):
         return None
-    return graph.fused_plan_img16()
+    return graph.fused_plan_rank1() if rank1 else graph.fused_plan_img16()
+
+
+def _adjoint_plan16(graph, rank1=False):
+    """_forward_plan16 for the adjoint graph (S^T, the BPTT's hops; rank1: the adjoint plan of the pattern + the swapped factors)."""
+    if os.environ.get('GCRNN_NO_IMG16'):
+        return None
+    return graph.fused_plan_rank1(adjoint=True) if rank1 else graph.fused_plan_img16(adjoint=True)
+
+
+def _fused_forward_steps(graph, xs, h0s, hs, wpack, b32, B, T, N, F, G, K, H, last_only, Xinline, st, gi=None, gf=None, evs=None, hw=None, part=None):
+    """The forward on the 16-feature step kernel (gcrnn_fused_forward_bf16; the launcher beside _fused_forward_wide). H: the user-layout
+    output the launches store themselves, or None; hw / part: the fused head's weights and its partial sums."""
+    plan = graph.fused_plan()
+    plan16 = _forward_plan16(graph)
+    check(lib.gcrnn_fused_forward_bf16(_p(xs), _p(h0s), _p(hs), _p(wpack), _p(b32), _p(gi), _p(gf), *_fused_graph_args(plan16 or plan),
+                                       B, T, N, F, G, K, _p(H), int(bool(last_only)) | (2 if plan16 else 0), evs, plan.get('uniform_w', 0.0),
+                                       _p(Xinline), _p(hw), _p(part), st), 'fused_forward')
+
+
+def fused_img16_plan(graph, gated, head):
+    """The bf16-image plan of the un-gated forward steps, or None (_forward_plan16; un-gated and time-gated cells, with or without the
+    fused head)."""
+    return _forward_plan16(graph)
 
 
 def _fused_graph_args(plan):
     return (_p(plan['tile_slots']), _p(plan['tile_off']), _p(plan['ell_addr']), _p(plan['ell_val']),
             _p(plan['ell_val4']), _p(plan['ell_col4']), plan['entries'])
+
+
+def _wide_graph_args(plan16):
+    return _p(plan16['tile_slots']), _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries']
 
 
 _SIDE_STREAMS = {}
@@ -598,6 +625,37 @@ def fused_pad_taps(wA):
     F, G = wA.shape[0], wA.shape[3]
     Gp = fused_padded_inputs(F, G)
     return wA if Gp == G else torch.nn.functional.pad(wA, (0, Gp - G))
+
+
+def _pad_tap_count(w, K):
+    """Taps w [F][1][k][C] with zero taps appended up to K of them."""
+    k = w.shape[2]
+    return w if k == K else torch.cat([w, w.new_zeros(w.shape[0], 1, K - k, w.shape[3])], dim=2)
+
+
+def _transposed_taps(w):
+    """Taps w [F_out][1][K][F_in] -> [F_in][1][K][F_out]: the adjoint filter's (detached)."""
+    return w.detach()[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)
+
+
+def _pad_gate_inputs(wA_g, G):
+    """A gate sub-cell's input taps [F][1][K][g] with zero taps for the padded input channels (g < G = 32)."""
+    return wA_g if wA_g.shape[3] == G else torch.nn.functional.pad(wA_g.detach(), (0, G - wA_g.shape[3]))
+
+
+def _unpack_states(hs, H, last_only, N, st):
+    """The states hs [T][B][NPad][F] (the last one alone with last_only) into the user-layout H, where the kernels could not store it
+    themselves (N % 8 != 0: no 16-byte row stores)."""
+    T, B, npad, F = hs.shape
+    src = hs[T - 1:] if last_only else hs
+    check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(src), _p(H), B, 1 if last_only else T, F, N, npad, None, st), 'unpack_seq')
+
+
+def _unpack_grad(ds, B, T, C, N, st):
+    """A sequence-major gradient ds [T][B][NPad][C] bf16 in the user layout, [B][T][C][N] bf16."""
+    g = torch.empty((B, T, C, N), dtype=torch.bfloat16, device=ds.device)
+    check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(ds), _p(g), B, T, C, N, ds.shape[-2], None, st), 'unpack_seq')
+    return g
 
 
 def fused_pack_inputs(X, h0, graph, overlap=False, first_only=False, channels=None, states=True):
@@ -655,11 +713,35 @@ def fused_pack_inputs(X, h0, graph, overlap=False, first_only=False, channels=No
     return xs, hs_all, events
 
 
+class _PendingLayout(object):
+    """The part of X that fused_pack_inputs_gated left to the first gate pre-pass: xs [T][B][NPad][G] holds its leading `steps` time steps,
+    x_user is the user-layout tensor the rest comes from (None once settled). The cell entry points hand the object to their pre-passes
+    (`pending=`) and check that it is settled before the recurrence reads xs."""
+
+    def __init__(self, xs, x_user, steps):
+        self.xs, self.x_user, self.steps = xs, x_user, steps
+
+    @property
+    def settled(self):
+        return self.x_user is None
+
+    def settle(self, consumer_steps):
+        """The user-layout tensor a gate pre-pass should lay out while it runs, or None. The pending layout was sized for the pre-pass that
+        was expected to run first; when another one runs instead -- it does not lay out at this shape (consumer_steps <= 0), or counts on a
+        different number of leading steps -- the rest of X is laid out here, by the plain pack. Either way nothing is pending afterwards."""
+        x_user, self.x_user = self.x_user, None
+        if x_user is None or (consumer_steps > 0 and consumer_steps == self.steps):
+            return x_user
+        T, B, npad, G = self.xs.shape
+        check(lib.gcrnn_pack_seq_major_steps(_p(x_user), _p(self.xs), B, T, G, x_user.shape[3], npad, self.steps, T, 0, _stream()), 'pack_seq_steps')
+        return None
+
+
 def fused_pack_inputs_gated(X, h0, graph, F, K, states=True):
     """fused_pack_inputs for a cell whose FIRST consumer of xs is a gate pre-pass (fused_time_gate): on a uniform-weight graph with
     a batch that fills the chip, only the first time step(s) are laid out here and that pre-pass lays out the rest while it runs
     (gcrnn_fused_gate_prepass_pack_bf16: every item packs the operand of its workgroup's next item) -- the 0.5 ms pass over X at
-    B = 256, T = 32 goes away. The pending user-layout tensor travels with xs (`_pending_user`) until that pre-pass has run."""
+    B = 256, T = 32 goes away. Returns (xs, hs_all, pending): the _PendingLayout that pre-pass takes, or None when all of X is laid out."""
     B, T, G, N = X.shape
     plan = graph.fused_plan()
     plan16 = fused_img16_plan(graph, True, None)
@@ -667,34 +749,29 @@ def fused_pack_inputs_gated(X, h0, graph, F, K, states=True):
     if plan16 is not None and X.dtype == torch.bfloat16 and X.is_contiguous() and X.data_ptr() % 16 == 0 and not os.environ.get('GCRNN_NO_INLINE_PACK'):
         _, steps = fused_gate_pair_plan(graph, B, T, N, F, G, K, True)      # (the wide kernel's gate-pair pre-pass lays X out, when it takes the problem)
         if steps <= 0:
-            steps = int(lib.gcrnn_fused_gate_prepass_lays_out(B, T, N, F, G, K, plan16['entries'], plan.get('uniform_w', 0.0), 1))
+            steps = _gate_prepass_lays_out(plan, plan16, B, T, N, F, G, K)
     if steps <= 0 or steps >= T:
-        return fused_pack_inputs(X, h0, graph, states=states)
-    npad = plan['npad']
+        return fused_pack_inputs(X, h0, graph, states=states) + (None,)
+    xs, hs_all = _pack_leading_steps(X, h0, plan['npad'], F, steps, states)
+    return xs, hs_all, _PendingLayout(xs, X, steps)
+
+
+def _pack_leading_steps(X, h0, npad, F, steps, states=True):
+    """fused_pack_inputs with only the first `steps` time steps of the contiguous X laid out: the first consumer of xs lays out the rest."""
+    B, T, G, N = X.shape
     st = _stream()
     xs = torch.empty((T, B, npad, G), dtype=torch.bfloat16, device=X.device)
     hs_all = torch.empty(((T if states else 0) + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
     check(lib.gcrnn_pack_seq_major(_lib.BF16, _p(h0.contiguous()), _p(hs_all), B, 1, F, N, npad, None, st), 'pack_seq')
     check(lib.gcrnn_pack_seq_major_steps(_p(X), _p(xs), B, T, G, N, npad, 0, steps, 0, st), 'pack_seq_steps')
-    xs._pending_user = X
-    xs._pending_steps = steps
     return xs, hs_all
 
 
-def _pending_layout_for(xs, consumer_steps):
-    """The user-layout tensor a gate pre-pass should lay out while it runs (fused_pack_inputs_gated), or None. The pending layout was sized
-    for the pre-pass that was expected to run first; when another one runs instead -- it does not lay out at this shape (consumer_steps
-    <= 0), or counts on a different number of leading steps -- the rest of X is laid out here, by the plain pack, and nothing is pending."""
-    x_user = getattr(xs, '_pending_user', None)
-    if x_user is None:
-        return None
-    done = int(getattr(xs, '_pending_steps', 0))
-    if consumer_steps > 0 and consumer_steps == done:
-        return x_user
-    T, B, npad, G = xs.shape
-    check(lib.gcrnn_pack_seq_major_steps(_p(x_user), _p(xs), B, T, G, x_user.shape[3], npad, done, T, 0, _stream()), 'pack_seq_steps')
-    del xs._pending_user
-    return None
+def _gate_prepass_lays_out(plan, plan16, B, T, N, F, G, K):
+    """The leading time steps of xs the 16-feature gate pre-pass counts on when it lays out X itself (0: it does not at this shape)."""
+    if plan16 is None:
+        return 0
+    return int(lib.gcrnn_fused_gate_prepass_lays_out(B, T, N, F, G, K, plan16['entries'], plan.get('uniform_w', 0.0), 1))
 
 
 def fused_overlap_ok(X):
@@ -717,11 +794,11 @@ def fused_h0_zero_flag(h0):
     return (h0 == 0).all().to(torch.int32).view(1)
 
 
-def fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, store_states=False, hzero=None):
+def fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, store_states=False, hzero=None, pending=None):
     """One time gate of the fused path for all (t, b) (graphML.py:2357-2374): sigmoid(Linear(vec(tanh(A_g(S)x_t + B_g(S)h0
     + 2 b_g)))) as ONE pre-pass launch. xs [T][B][NPad][G], h0s [1][B][NPad][F] sequence-major bf16. hzero: device int32
-    flag (fused_h0_zero_flag), non-zero when h0 is all zeros -- the kernel then skips the state half of the operand. Returns the gate
-    [T][B] fp32 (and, with store_states, the gate cell's states c [T][B][NPad][F] bf16 for its BPTT)."""
+    flag (fused_h0_zero_flag), non-zero when h0 is all zeros -- the kernel then skips the state half of the operand. pending: the
+    _PendingLayout of xs (fused_pack_inputs_gated), settled here. Returns the gate [T][B] fp32 (and, with store_states, the gate cell's states c [T][B][NPad][F] bf16 for its BPTT)."""
     T, B, npad, G = xs.shape
     F = wA_g.shape[0]
     K = max(wA_g.shape[2], wB_g.shape[2])
@@ -733,16 +810,12 @@ def fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, store_s
     parts = torch.empty((T * B, (F // 16) * int(lib.gcrnn_fused_step_waves())), dtype=torch.float32, device=xs.device)
     cs = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=xs.device) if store_states else None
     plan16 = fused_img16_plan(graph, True, None)
-    x_user = None
-    if getattr(xs, '_pending_user', None) is not None:
-        lays = int(lib.gcrnn_fused_gate_prepass_lays_out(B, T, N, F, G, K, plan16['entries'], plan.get('uniform_w', 0.0), 1)) if plan16 is not None else 0
-        x_user = _pending_layout_for(xs, lays)
+    x_user = pending.settle(_gate_prepass_lays_out(plan, plan16, B, T, N, F, G, K)) if pending is not None else None
     if x_user is not None:
         # xs holds its first time step(s) only (fused_pack_inputs_gated): this pre-pass lays out the rest
         check(lib.gcrnn_fused_gate_prepass_pack_bf16(_p(x_user), _p(xs), _p(h0s), _p(wp), _p(bg), _p(gw), _p(parts), _p(cs),
                                                      *_fused_graph_args(plan16), B, T, N, F, G, K, _p(hzero), plan.get('uniform_w', 0.0),
                                                      1, st), 'gate_prepass_pack')
-        del xs._pending_user
     else:
         check(lib.gcrnn_fused_gate_prepass_bf16(_p(xs), _p(h0s), _p(wp), _p(bg), _p(gw), _p(parts), _p(cs),
                                                 *_fused_graph_args(plan16 or plan), B, T, N, F, G, K, _p(hzero), plan.get('uniform_w', 0.0),
@@ -754,12 +827,18 @@ def fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, store_s
     return (gate, cs, gw) if store_states else gate
 
 
+def _fused_time_gates_each(xs, h0s, gates, graph, N, hzero, pending=None):
+    """(gi, gf) of fused_time_gate, one pre-pass launch per gate; the gates' input taps are padded to the channels of xs."""
+    return tuple(fused_time_gate(xs, h0s, _pad_gate_inputs(g[0], xs.shape[3]), *g[1:], graph, N, hzero=hzero, pending=pending)
+                 for g in (gates['in'], gates['forget']))
+
+
 def fused_gate_pair_plan(graph, B, T, N, F, G, K, with_pack):
     """(plan16, steps) when the wide kernel's gate-PAIR pre-pass takes this problem (gcrnn_fused_gate_pair_prepass_wide_bf16: both time
     gates of every (t, b) in ONE launch), else (None, 0). steps: with_pack -- the leading time steps of xs the caller lays out itself."""
-    plan16 = fused_img16_plan(graph, True, None)
-    if plan16 is None and not os.environ.get('GCRNN_NO_IMG16'):
-        plan16 = graph.fused_plan_rank1()                # rank-1-weighted graph (normalised adjacency): the plan of its 0/1 pattern + the factor tables
+    plan16 = _forward_plan16(graph)
+    if plan16 is None:
+        plan16 = _forward_plan16(graph, rank1=True)
     if plan16 is None or F % 32 or G % 32 or os.environ.get('GCRNN_NO_GATE_PAIR'):
         return None, 0
     steps = int(lib.gcrnn_fused_gate_pair_wide_supported(int(B), int(T), int(N), int(F), int(G), int(K), int(plan16['entries']),
@@ -767,18 +846,16 @@ def fused_gate_pair_plan(graph, B, T, N, F, G, K, with_pack):
     return (plan16, steps) if steps > 0 else (None, 0)
 
 
-def fused_time_gate_pair(xs, h0s, gate_in, gate_f, graph, N, store_states=False, hzero=None):
+def fused_time_gate_pair(xs, h0s, gate_in, gate_f, graph, N, store_states=False, hzero=None, pending=None):
     """BOTH time gates of the fused path for all (t, b) (graphML.py:2357-2374) as ONE pre-pass launch of the wide sequence-resident kernel: the
     two sub-cells run as one cell of 2 F outputs, so an item's operand (x_t, h0) is loaded -- and, when xs still waits for its layout
-    (`_pending_user`), laid out -- once. gate_* = (wA_g, wB_g, bias_g, lin_w, lin_b). Returns (gi, gf) [T][B] fp32, and with store_states
+    (pending: its _PendingLayout), laid out -- once. gate_* = (wA_g, wB_g, bias_g, lin_w, lin_b). Returns (gi, gf) [T][B] fp32, and with store_states
     also ((cs_in, gw_in), (cs_f, gw_f)): the sub-cells' states [T][B][NPad][F] bf16 and the read-out weights [N][F] fp32 for their BPTT."""
     T, B, npad, G = xs.shape
     F = gate_in[0].shape[0]
     K = max(gate_in[0].shape[2], gate_in[1].shape[2])
     st = _stream()
-    x_user = None
-    if getattr(xs, '_pending_user', None) is not None:
-        x_user = _pending_layout_for(xs, fused_gate_pair_plan(graph, B, T, N, F, G, K, True)[1])
+    x_user = pending.settle(fused_gate_pair_plan(graph, B, T, N, F, G, K, True)[1]) if pending is not None else None
     plan16, _ = fused_gate_pair_plan(graph, B, T, N, F, G, K, x_user is not None)
     assert plan16 is not None
     def prepare():      # everything derived from the gates' parameters alone: cached while they are unchanged (_cached_pack)
@@ -798,10 +875,7 @@ def fused_time_gate_pair(xs, h0s, gate_in, gate_f, graph, N, store_states=False,
     cs_in = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=xs.device) if store_states else None
     cs_f = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=xs.device) if store_states else None
     check(lib.gcrnn_fused_gate_pair_prepass_wide_bf16(_p(x_user), _p(xs), _p(h0s), _p(wp), _p(b2), _p(gw2), _p(parts), _p(cs_in), _p(cs_f),
-                                                      _p(plan16['tile_slots']), _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries'],
-                                                      B, T, N, F, G, K, _p(hzero), _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st), 'gate_pair_prepass')
-    if x_user is not None:
-        del xs._pending_user
+                                                      *_wide_graph_args(plan16), B, T, N, F, G, K, _p(hzero), _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st), 'gate_pair_prepass')
     # read-out finish in ONE launch (round 5; until round 4 five torch launches): partials added in a fixed order, + bias, sigmoid
     out = [torch.empty((T, B), dtype=torch.float32, device=xs.device) for _ in range(2)]
     lbp = [(lb.reshape(-1).contiguous() if lb is not None else None) for lb in lbs]
@@ -851,7 +925,7 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     dev = X.device
     X = X.contiguous()
     h0 = h0.contiguous()
-    events = None
+    events = pending = None
     inline = False
     # inference through the user-layout H: the wide kernel then runs without a state image (fused_state_scratch) and hs is not allocated
     # here; a path that does need it allocates it below
@@ -868,7 +942,7 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     elif gates is None and fused_overlap_ok(X):          # (the gate pre-passes read every x_t at once: nothing to hide behind)
         xs, hs_all, events = fused_pack_inputs(X, h0, graph, overlap=True, states=not lean)
     elif gates is not None and gate_values is None:
-        xs, hs_all = fused_pack_inputs_gated(X, h0, graph, F, K, states=not lean)       # (the first gate pre-pass lays out x_1 .. x_{T-1})
+        xs, hs_all, pending = fused_pack_inputs_gated(X, h0, graph, F, K, states=not lean)       # (the first gate pre-pass lays out x_1 .. x_{T-1})
     else:
         xs, hs_all = fused_pack_inputs(X, h0, graph, states=not lean)
     h0s, hs = hs_all[:1], hs_all[1:]
@@ -878,22 +952,18 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
         assert tuple(gi.shape) == (T, B) and tuple(gf.shape) == (T, B)
     elif gates is not None:
         hzero = fused_h0_zero_flag(h0)
-        g = {}
         gp = {}
         for name in ('in', 'forget'):
             wA_g, wB_g, bias_g, lin_w, lin_b = gates[name]
-            if wA_g.shape[3] != G:
-                wA_g = torch.nn.functional.pad(wA_g.detach(), (0, G - wA_g.shape[3]))
+            wA_g = _pad_gate_inputs(wA_g, G)
             assert max(wA_g.shape[2], wB_g.shape[2]) == K and wA_g.shape[0] == F
             gp[name] = (wA_g, wB_g, bias_g, lin_w, lin_b)
-        pair16, _ = fused_gate_pair_plan(graph, B, T, N, F, G, K, getattr(xs, '_pending_user', None) is not None)
+        pair16, _ = fused_gate_pair_plan(graph, B, T, N, F, G, K, pending is not None)
         if pair16 is not None:
-            gi, gf = fused_time_gate_pair(xs, h0s, gp['in'], gp['forget'], graph, N, hzero=hzero)      # ONE launch for both gates
+            gi, gf = fused_time_gate_pair(xs, h0s, gp['in'], gp['forget'], graph, N, hzero=hzero, pending=pending)      # ONE launch for both gates
         else:
-            for name in ('in', 'forget'):
-                g[name] = fused_time_gate(xs, h0s, *gp[name], graph, N, hzero=hzero)
-            gi, gf = g['in'], g['forget']
-    assert getattr(xs, '_pending_user', None) is None
+            gi, gf = _fused_time_gates_each(xs, h0s, gp, graph, N, hzero, pending)
+    assert pending is None or pending.settled
     b32 = _bias_f32(bias, st)
     direct = (N % 8 == 0)                 # the step kernels write the user layout themselves (16-byte row stores)
     evs = None
@@ -904,11 +974,8 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
         hw = head[0].detach().float().reshape(-1).contiguous()
         assert hw.numel() == F
         part = torch.empty((T, B, F // 16, N), dtype=torch.float32, device=dev)
-        plan16 = fused_img16_plan(graph, gi is not None, head)
         wpack = _fused_pack_weights(wA, wB, st)
-        check(lib.gcrnn_fused_forward_bf16(_p(xs), _p(h0s), _p(hs), _p(wpack), _p(b32), _p(gi), _p(gf), *_fused_graph_args(plan16 or plan),
-                                           B, T, N, F, G, K, None, 2 if plan16 else 0, evs, plan.get('uniform_w', 0.0), _p(X) if inline else None,
-                                           _p(hw), _p(part), st), 'fused_forward')
+        _fused_forward_steps(graph, xs, h0s, hs, wpack, b32, B, T, N, F, G, K, None, False, X if inline else None, st, gi, gf, evs, hw, part)
         y = part.sum(dim=2)                                          # fixed order over the F / 16 chunks
         if head[1] is not None:
             y = y + head[1].detach().float().reshape(())
@@ -927,31 +994,22 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
             hs = torch.empty((T,) + tuple(h0s.shape[1:]), dtype=torch.bfloat16, device=dev)
         _fused_forward_wide(wide, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H if direct else None, last_only, X if inline else None, st, gi=gi, gf=gf, scratch=scr)
         if not direct:
-            src = hs[T - 1:] if last_only else hs
-            check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(src), _p(H), B, 1 if last_only else T, F, N, plan['npad'], None, st), 'unpack_seq')
+            _unpack_states(hs, H, last_only, N, st)
         if return_states:
             return hs_all, plan, H
         return H
     if hs.shape[0] == 0:                                 # (lean, and not the wide kernel after all: the step kernels keep the state image)
         hs = torch.empty((T,) + tuple(h0s.shape[1:]), dtype=torch.bfloat16, device=dev)
-    plan16 = fused_img16_plan(graph, gi is not None, None)
     wpack = _fused_pack_weights(wA, wB, st)
     if native_out:
         assert not return_states
-        check(lib.gcrnn_fused_forward_bf16(_p(xs), _p(h0s), _p(hs), _p(wpack), _p(b32), _p(gi), _p(gf), *_fused_graph_args(plan16 or plan),
-                                           B, T, N, F, G, K, None, (2 if plan16 else 0), evs,
-                                           plan.get('uniform_w', 0.0), _p(X) if inline else None, None, None, st),
-              'fused_forward')
+        _fused_forward_steps(graph, xs, h0s, hs, wpack, b32, B, T, N, F, G, K, None, False, X if inline else None, st, gi, gf, evs)
         Hv = hs.permute(1, 0, 3, 2)[:, :, :, :N]                     # B x T x F x N, strides of the sequence-major image
         return Hv[:, T - 1:] if last_only else Hv
     H = torch.empty((B, 1 if last_only else T, F, N), dtype=torch.bfloat16, device=dev)
-    check(lib.gcrnn_fused_forward_bf16(_p(xs), _p(h0s), _p(hs), _p(wpack), _p(b32), _p(gi), _p(gf), *_fused_graph_args(plan16 or plan),
-                                       B, T, N, F, G, K, _p(H) if direct else None, int(last_only) | (2 if plan16 else 0), evs,
-                                       plan.get('uniform_w', 0.0), _p(X) if inline else None, None, None, st),
-          'fused_forward')
+    _fused_forward_steps(graph, xs, h0s, hs, wpack, b32, B, T, N, F, G, K, H if direct else None, last_only, X if inline else None, st, gi, gf, evs)
     if not direct:
-        src = hs[T - 1:] if last_only else hs
-        check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(src), _p(H), B, 1 if last_only else T, F, N, plan['npad'], None, st), 'unpack_seq')
+        _unpack_states(hs, H, last_only, N, st)
     if return_states:
         return hs_all, plan, H
     return H
@@ -981,10 +1039,7 @@ def fused_cell_forward_native(xs, h0s, wA, wB, bias, graph, N):
     if wide is not None:
         _fused_forward_wide(wide, xs, hs_all[:1], hs_all[1:], wA, wB, b32, B, T, N, F, G, K, None, False, None, st)
         return hs_all[1:]
-    plan16 = fused_img16_plan(graph, False, None)
-    check(lib.gcrnn_fused_forward_bf16(_p(xs), _p(hs_all[:1]), _p(hs_all[1:]), _p(wpack), _p(b32), None, None, *_fused_graph_args(plan16 or plan),
-                                       B, T, N, F, G, K, None, (2 if plan16 else 0), None, plan.get('uniform_w', 0.0), None, None, None, st),
-          'fused_forward')
+    _fused_forward_steps(graph, xs, hs_all[:1], hs_all[1:], wpack, b32, B, T, N, F, G, K, None, False, None, st)
     return hs_all[1:]
 
 
@@ -1007,10 +1062,7 @@ def fused_filter_output(xs, w, bias, graph, K, N, adjoint=False):
     T, B, npad, Cin = xs.shape
     F = w.shape[0]
     plan = graph.fused_plan(adjoint=adjoint)
-    if adjoint:
-        plan16 = None if os.environ.get('GCRNN_NO_IMG16') else graph.fused_plan_img16(adjoint=True)
-    else:
-        plan16 = fused_img16_plan(graph, False, None)
+    plan16 = _adjoint_plan16(graph) if adjoint else _forward_plan16(graph)
     st = _stream()
     b32 = _bias_f32(bias, st)
     out = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=xs.device)
@@ -1021,9 +1073,7 @@ def fused_filter_output(xs, w, bias, graph, K, N, adjoint=False):
               'fused_filter_output')
     else:
         def pack_x():
-            wd = w.detach()
-            if wd.shape[2] < K:
-                wd = torch.cat([wd, wd.new_zeros(F, 1, K - wd.shape[2], Cin)], dim=2)
+            wd = _pad_tap_count(w.detach(), K)
             return _fused_pack_weights(wd, wd.new_zeros((F, 1, K, F)), st), torch.zeros((1, npad, F), dtype=torch.bfloat16, device=xs.device)
         wp, zero_h = _cached_pack('filtertaps_x', (w.detach(),), (int(K), int(npad)), st, pack_x)
         check(lib.gcrnn_fused_filter_output_bf16(_p(zero_h), _p(xs), _p(wp), _p(b32), _p(out), *_fused_graph_args(plan16 or plan), B, T, N, F, Cin, K,
@@ -1083,22 +1133,21 @@ def _tap_fragments(wf, F):
     return pl.view(3, 16, F // 16, 4, 4).permute(2, 0, 3, 1, 4).contiguous()
 
 
-def fused_node_gate_taps(xs, h0s, wA_g, wB_g, bias_g, wf, graph, N, hzero=None):
+def fused_node_gate_taps(xs, h0s, wA_g, wB_g, bias_g, wf, graph, N, hzero=None, pending=None):
     """Gate cell of a node gate at inference with the per-tap dot products of its F -> 1 filter fused into the pre-pass
     (gcrnn_fused_gate_prepass_taps_bf16): returns s [T*B][K][1][N] fp32, or None where the fused pre-pass does not apply (the caller
-    then stores the states and runs gcrnn_node_gate_dot over them). Lays out X too when xs carries a pending user-layout tensor."""
+    then stores the states and runs gcrnn_node_gate_dot over them). Lays out X too when xs still waits for its layout (pending: its _PendingLayout)."""
     T, B, npad, G = xs.shape
     F = wA_g.shape[0]
     K = max(wA_g.shape[2], wB_g.shape[2])
     Kt = wf.shape[2]
     plan = graph.fused_plan()
     plan16 = fused_img16_plan(graph, True, None)
-    x_user = None
-    if getattr(xs, '_pending_user', None) is not None:
-        lays = int(lib.gcrnn_fused_gate_prepass_lays_out(B, T, N, F, G, K, plan16['entries'], plan.get('uniform_w', 0.0), 1)) if plan16 is not None else 0
-        x_user = _pending_layout_for(xs, lays)
+    x_user = pending.settle(_gate_prepass_lays_out(plan, plan16, B, T, N, F, G, K)) if pending is not None else None
     if plan16 is None or os.environ.get('GCRNN_NO_FUSED_TAPS') or not int(lib.gcrnn_fused_gate_prepass_taps_supported(
             B, T, N, F, G, K, plan16['entries'], plan.get('uniform_w', 0.0), 1, 1 if x_user is not None else 0, Kt)):
+        if x_user is not None:
+            pending.x_user = x_user      # not laid out here after all: still pending, for the pre-pass the caller runs instead
         return None
     st = _stream()
     wp = _fused_pack_weights(wA_g.detach(), wB_g.detach(), st)
@@ -1108,8 +1157,6 @@ def fused_node_gate_taps(xs, h0s, wA_g, wB_g, bias_g, wf, graph, N, hzero=None):
     check(lib.gcrnn_fused_gate_prepass_taps_bf16(_p(x_user), _p(xs), _p(h0s), _p(wp), _p(bg), _p(frags), _p(s), Kt, None,
                                                  *_fused_graph_args(plan16), B, T, N, F, G, K, _p(hzero), plan.get('uniform_w', 0.0), 1, st),
           'gate_prepass_taps')
-    if x_user is not None:
-        del xs._pending_user
     return s
 
 
@@ -1131,7 +1178,7 @@ def _tap_fragments32(wfs, F):
     return torch.stack(out, dim=0).contiguous()
 
 
-def fused_node_gate_taps_pair(xs, h0s, gate_in, gate_f, graph, N, hzero=None):
+def fused_node_gate_taps_pair(xs, h0s, gate_in, gate_f, graph, N, hzero=None, pending=None):
     """BOTH node gates' cells of every (t, b) with the per-tap dot products of their F -> 1 filters, as ONE pre-pass launch of the wide
     sequence-resident kernel (gcrnn_fused_gate_pair_prepass_taps_wide_bf16; inference). gate_* = (wA_g, wB_g, bias_g, wf, bf) as in
     fused_node_cell_forward. Returns (s_in, s_f), each [T*B][K][1][N] fp32, or None where the wide pre-pass does not apply."""
@@ -1141,19 +1188,16 @@ def fused_node_gate_taps_pair(xs, h0s, gate_in, gate_f, graph, N, hzero=None):
     Kt = gate_in[3].shape[2]
     if gate_f[3].shape[2] != Kt or max(gate_f[0].shape[2], gate_f[1].shape[2]) != K or os.environ.get('GCRNN_NO_NODE_GATE_PAIR'):
         return None
-    if fused_gate_pair_plan(graph, B, T, N, F, G, K, getattr(xs, '_pending_user', None) is not None)[0] is None:
+    if fused_gate_pair_plan(graph, B, T, N, F, G, K, pending is not None and not pending.settled)[0] is None:
         return None
-    x_user = None
-    if getattr(xs, '_pending_user', None) is not None:
-        x_user = _pending_layout_for(xs, fused_gate_pair_plan(graph, B, T, N, F, G, K, True)[1])
+    x_user = pending.settle(fused_gate_pair_plan(graph, B, T, N, F, G, K, True)[1]) if pending is not None else None
     plan16, _ = fused_gate_pair_plan(graph, B, T, N, F, G, K, x_user is not None)
     if plan16 is None:
         return None
     st = _stream()
 
     def prepare():
-        padx = lambda w: w.detach() if w.shape[3] == G else torch.nn.functional.pad(w.detach(), (0, G - w.shape[3]))      # (G < 32: zero input taps for the padded channels)
-        wA2 = torch.cat([padx(gate_in[0]), padx(gate_f[0])], dim=0)
+        wA2 = torch.cat([_pad_gate_inputs(gate_in[0].detach(), G), _pad_gate_inputs(gate_f[0].detach(), G)], dim=0)
         wB2 = torch.cat([gate_in[1].detach(), gate_f[1].detach()], dim=0)
         wp_ = _fused_pack_weights_wide(wA2, wB2, plan16['uniform_w'], st)
         zb = torch.zeros(F, dtype=torch.float32, device=xs.device)
@@ -1164,11 +1208,8 @@ def fused_node_gate_taps_pair(xs, h0s, gate_in, gate_f, graph, N, hzero=None):
     nch = F // 32
     parts = torch.empty((T * B, 2, nch, Kt, N), dtype=torch.float32, device=xs.device)
     check(lib.gcrnn_fused_gate_pair_prepass_taps_wide_bf16(_p(x_user), _p(xs), _p(h0s), _p(wp), _p(b2), _p(frags), _p(parts), Kt, None, None,
-                                                           _p(plan16['tile_slots']), _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries'],
-                                                           B, T, N, F, G, K, _p(hzero), _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
+                                                           *_wide_graph_args(plan16), B, T, N, F, G, K, _p(hzero), _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
           'gate_pair_prepass_taps')
-    if x_user is not None:
-        del xs._pending_user
     return parts.view(T * B * 2, nch, Kt, 1, N)                         # row 2 i + g: item i, gate g; [.., chunk, tap, 1, node]: the caller's layout pass adds the chunks
 
 
@@ -1190,12 +1231,12 @@ def fused_node_cell_forward(X, h0, wA, wB, bias, graph, node_gates, time_gates=N
     K = max(Kin, Kst)
     plan = graph.fused_plan()
     st = _stream()
-    xs, hs_all = fused_pack_inputs_gated(X.contiguous(), h0.contiguous(), graph, F, K)      # (the first gate cell's pre-pass lays out the rest of X)
+    xs, hs_all, pending = fused_pack_inputs_gated(X.contiguous(), h0.contiguous(), graph, F, K)      # (the first gate cell's pre-pass lays out the rest of X)
     h0s, hs = hs_all[:1], hs_all[1:]
     hzero = fused_h0_zero_flag(h0)
     zero_lin = torch.zeros((1, F * N), dtype=torch.float32, device=X.device)
     ng = []
-    pair = fused_node_gate_taps_pair(xs, h0s, node_gates['in'], node_gates['forget'], graph, N, hzero=hzero)      # both gate cells in ONE launch (wide kernel)
+    pair = fused_node_gate_taps_pair(xs, h0s, node_gates['in'], node_gates['forget'], graph, N, hzero=hzero, pending=pending)      # both gate cells in ONE launch (wide kernel)
     ngates = None
     if pair is not None and not os.environ.get('GCRNN_NO_NODE_GATE_FILTER') and int(lib.gcrnn_node_gate_filter_supported(pair.shape[2], N, graph.fwd[0].nnz, plan.get('uniform_w', 0.0))):
         # second stage of both F -> 1 filters in ONE pass over the tap dots: chunk sum, the K - 1 one-channel hops (running signal in LDS),
@@ -1217,27 +1258,20 @@ def fused_node_cell_forward(X, h0, wA, wB, bias, graph, node_gates, time_gates=N
             ng.append(torch.sigmoid(l1 + bf.detach().float().view(()) if bf is not None else l1))
     for name in (() if pair is not None else ('in', 'forget')):
         wA_g, wB_g, bias_g, wf, bf = node_gates[name]
-        if wA_g.shape[3] != G:
-            wA_g = torch.nn.functional.pad(wA_g.detach(), (0, G - wA_g.shape[3]))
-        staps = fused_node_gate_taps(xs, h0s, wA_g, wB_g, bias_g, wf, graph, N, hzero=hzero)
+        wA_g = _pad_gate_inputs(wA_g, G)
+        staps = fused_node_gate_taps(xs, h0s, wA_g, wB_g, bias_g, wf, graph, N, hzero=hzero, pending=pending)
         if staps is not None:          # the filter's tap dots came out of the pre-pass itself: no state array, no pass over it
             logit = _node_gate_logits_from_taps(staps, bf, graph, T, B, N)
         else:
-            _, cs, _ = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, zero_lin, None, graph, N, store_states=True, hzero=hzero)
+            _, cs, _ = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, zero_lin, None, graph, N, store_states=True, hzero=hzero, pending=pending)
             logit, _ = node_gate_logits(cs, wf, bf, graph, N)
         ng.append(torch.sigmoid(logit))
     if ngates is None:
         ngates = torch.stack(ng, dim=1).contiguous()                    # [T][2][B][N]
-    assert getattr(xs, '_pending_user', None) is None
+    assert pending is None or pending.settled
     gi = gf = None
     if time_gates is not None:
-        g = {}
-        for name in ('in', 'forget'):
-            wA_g, wB_g, bias_g, lin_w, lin_b = time_gates[name]
-            if wA_g.shape[3] != G:
-                wA_g = torch.nn.functional.pad(wA_g.detach(), (0, G - wA_g.shape[3]))
-            g[name] = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, hzero=hzero)
-        gi, gf = g['in'], g['forget']
+        gi, gf = _fused_time_gates_each(xs, h0s, time_gates, graph, N, hzero)
     plan16 = fused_img16_plan(graph, False, None)
     uw = float(plan.get('uniform_w', 0.0))
     b32 = _bias_f32(bias, st)
@@ -1246,24 +1280,23 @@ def fused_node_cell_forward(X, h0, wA, wB, bias, graph, node_gates, time_gates=N
     if plan16 is not None and F % 32 == 0 and G % 32 == 0 and lib.gcrnn_fused_filter_output_wide_supported(B, T, N, F, G, K, int(plan16['entries']), uw, 1, 0):
         wpx = _fused_pack_weights_wide(wA.detach(), wA.new_zeros((F, 1, K, F)), uw, st)      # (zero state taps, K of them: the pack's tap count is the kernel's)
         yx = torch.empty((T, B, plan['npad'], F), dtype=torch.bfloat16, device=X.device)
-        check(lib.gcrnn_fused_filter_output_wide_bf16(_p(xs), _p(wpx), _p(b32), _p(yx), _p(plan16['tile_slots']), _p(plan16['tile_off']),
-                                                      _p(plan16['ell_col4']), plan16['entries'], B, T, N, F, G, K, None, st), 'fused_filter_output_wide')
+        check(lib.gcrnn_fused_filter_output_wide_bf16(_p(xs), _p(wpx), _p(b32), _p(yx), *_wide_graph_args(plan16), B, T, N, F, G, K, None, st),
+              'fused_filter_output_wide')
     else:
         yx = fused_filter_output(xs, wA, bias, graph, K, N)
     H = torch.empty((B, 1 if last_only else T, F, N), dtype=torch.bfloat16, device=X.device)
     direct = (N % 8 == 0)
     if plan16 is not None and F % 32 == 0 and lib.gcrnn_fused_node_forward_wide_supported(B, T, N, F, K, int(plan16['entries']), uw, 1):
-        wBk = wB.detach() if Kst == K else torch.cat([wB.detach(), wB.new_zeros(F, 1, K - Kst, F)], dim=2)
+        wBk = _pad_tap_count(wB.detach(), K)
         wpBw = _fused_pack_weights_wide(wB.new_zeros((F, 1, 1, 0)), wBk, uw, st)      # (state-only operand: G = 0)
-        check(lib.gcrnn_fused_node_forward_wide_bf16(_p(h0s), _p(hs), _p(yx), _p(ngates), _p(gi), _p(gf), _p(wpBw), _p(b32), _p(plan16['tile_slots']),
-                                                     _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries'], B, T, N, F, K,
+        check(lib.gcrnn_fused_node_forward_wide_bf16(_p(h0s), _p(hs), _p(yx), _p(ngates), _p(gi), _p(gf), _p(wpBw), _p(b32),
+                                                     *_wide_graph_args(plan16), B, T, N, F, K,
                                                      _p(H) if direct else None, int(last_only), st), 'fused_node_forward_wide')
         if not direct:
-            src = hs[T - 1:] if last_only else hs
-            check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(src), _p(H), B, 1 if last_only else T, F, N, plan['npad'], None, st), 'unpack_seq')
+            _unpack_states(hs, H, last_only, N, st)
         return H
     def pack_state():
-        wBk = wB.detach() if Kst == K else torch.cat([wB.detach(), wB.new_zeros(F, 1, K - Kst, F)], dim=2)
+        wBk = _pad_tap_count(wB.detach(), K)
         return _fused_pack_state_taps(wBk, K, st)
     wpB = _cached_pack('statetaps', (wB.detach(),), int(K), st, pack_state)
     check(lib.gcrnn_fused_node_forward_bf16(_p(h0s), _p(hs), _p(yx), _p(ngates), _p(gi), _p(gf), _p(wpB), _p(b32), None,
@@ -1271,8 +1304,7 @@ def fused_node_cell_forward(X, h0, wA, wB, bias, graph, node_gates, time_gates=N
                                             int(last_only) | (2 if plan16 else 0), plan.get('uniform_w', 0.0), st),
           'fused_node_forward')
     if not direct:
-        src = hs[T - 1:] if last_only else hs
-        check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(src), _p(H), B, 1 if last_only else T, F, N, plan['npad'], None, st), 'unpack_seq')
+        _unpack_states(hs, H, last_only, N, st)
     return H
 
 
@@ -1284,10 +1316,10 @@ class _FusedNodeGate(torch.autograd.Function):
                gradient in place), then the weight-gradient kernel with h0 as every item's state operand. No gradient for X / h0."""
 
     @staticmethod
-    def forward(ctx, xs, h0s, X, h0, wA_g, wB_g, bias_g, wf, bf, graph, hzero):
+    def forward(ctx, xs, h0s, X, h0, wA_g, wB_g, bias_g, wf, bf, graph, hzero, pending=None):
         N, F = X.shape[3], wA_g.shape[0]
         zero_lin = torch.zeros((1, F * N), dtype=torch.float32, device=X.device)
-        _, cs, _ = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, zero_lin, None, graph, N, store_states=True, hzero=hzero)
+        _, cs, _ = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, zero_lin, None, graph, N, store_states=True, hzero=hzero, pending=pending)
         logit, wk = node_gate_logits(cs, wf, bf, graph, N)
         gate = torch.sigmoid(logit)
         ctx.save_for_backward(X, h0, wA_g, wB_g, bias_g, wf, bf, gate, cs, wk, hzero)
@@ -1325,7 +1357,7 @@ class _FusedNodeGate(torch.autograd.Function):
         gA = dW[:, :Kin, F:].unsqueeze(1).to(wA_g.dtype) if ctx.needs_input_grad[4] else None
         gB = dW[:, :Kst, :F].unsqueeze(1).to(wB_g.dtype) if ctx.needs_input_grad[5] else None
         gb = dbs.view_as(bias_g).to(bias_g.dtype) if (bias_g is not None and ctx.needs_input_grad[6]) else None
-        return None, None, None, None, gA, gB, gb, gwf, gbf, None, None
+        return None, None, None, None, gA, gB, gb, gwf, gbf, None, None, None
 
 
 class _FusedNodeCell(torch.autograd.Function):
@@ -1346,7 +1378,7 @@ class _FusedNodeCell(torch.autograd.Function):
         ngates = torch.stack([ni.detach().float(), nf.detach().float()], dim=1).contiguous()
         gic = gi.detach().float().contiguous() if gi is not None else None
         gfc = gf.detach().float().contiguous() if gf is not None else None
-        wBk = wB.detach() if Kst == K else torch.cat([wB.detach(), wB.new_zeros(F, 1, K - Kst, F)], dim=2)
+        wBk = _pad_tap_count(wB.detach(), K)
         wpB = _fused_pack_state_taps(wBk, K, st)
         b32 = bias.detach().float().contiguous().view(-1) if bias is not None else None
         H = torch.empty((B, T, F, N), dtype=torch.bfloat16, device=X.device)
@@ -1373,11 +1405,11 @@ class _FusedNodeCell(torch.autograd.Function):
         dH = dH.to(torch.bfloat16).contiguous()
         dHs, dHu = fused_pack_upstream(dH, graph, K)
         ngf = (ngates[:, 1] * gf.unsqueeze(2)).contiguous() if gf is not None else ngates[:, 1].contiguous()       # [T][B][N]
-        wBk = wB.detach() if Kst == K else torch.cat([wB.detach(), wB.new_zeros(F, 1, K - Kst, F)], dim=2)
-        wBt = wBk[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)                      # transposed taps [F_in][1][K][F_out]
+        wBk = _pad_tap_count(wB.detach(), K)
+        wBt = _transposed_taps(wBk)                                                     # [F_in][1][K][F_out]
         wpT = _fused_pack_state_taps(wBt, K, st)
         aplan = graph.fused_plan(adjoint=True)
-        aplan16 = None if os.environ.get('GCRNN_NO_IMG16') else graph.fused_plan_img16(adjoint=True)
+        aplan16 = _adjoint_plan16(graph)
         dpre = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=X.device)
         dyh = torch.empty_like(dpre)
         check(lib.gcrnn_fused_node_backward_data_bf16(_p(dHs), _p(hs), _p(dpre), _p(dyh), _p(ngf), _p(wpT), *_fused_graph_args(aplan16 or aplan),
@@ -1406,11 +1438,11 @@ def fused_node_cell_train(X, h0, wA, wB, bias, graph, node_gates, time_gates=Non
     autograd node of its own (_FusedNodeGate / _FusedTimeGate) and enters the cell (_FusedNodeCell) as a differentiable input."""
     require_device(X, h0, wA, wB, bias)
     with torch.no_grad():
-        xs, hs_all = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
+        xs, hs_all, pending = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
         hzero = fused_h0_zero_flag(h0)
-    ni = _FusedNodeGate.apply(xs, hs_all[:1], X, h0, *node_gates['in'], graph, hzero)
+    ni = _FusedNodeGate.apply(xs, hs_all[:1], X, h0, *node_gates['in'], graph, hzero, pending)
     nf = _FusedNodeGate.apply(xs, hs_all[:1], X, h0, *node_gates['forget'], graph, hzero)
-    assert getattr(xs, '_pending_user', None) is None          # (the first pre-pass laid out the rest of X)
+    assert pending is None or pending.settled                   # (the first pre-pass laid out the rest of X)
     gi = gf = None
     if time_gates is not None:
         gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, time_gates, graph, hzero)
@@ -1466,7 +1498,7 @@ def fused_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, time_gate
     st = _stream()
     x_pending = None
     if time_gates is not None:      # (the first time-gate pre-pass lays out the rest of X)
-        xs, hs_all = fused_pack_inputs_gated(X.contiguous(), h0.contiguous(), graph, F, K)
+        xs, hs_all, pending = fused_pack_inputs_gated(X.contiguous(), h0.contiguous(), graph, F, K)
     else:
         # (round 5) without time gates the first consumer of xs is the x branch's filter pass: when the wide kernel takes it, only the leading
         # time step(s) are laid out here and its items lay out the rest while they run -- no separate pass over X (0.5 ms at B = 256, T = 32)
@@ -1477,24 +1509,15 @@ def fused_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, time_gate
                 and not os.environ.get('GCRNN_NO_INLINE_PACK')):
             steps = int(lib.gcrnn_fused_filter_output_wide_supported(B, T, N, F, G, K, int(p16_['entries']), float(plan.get('uniform_w', 0.0)), 1, 1))
         if 0 < steps < T:
-            st0 = _stream()
-            xs = torch.empty((T, B, npad, G), dtype=torch.bfloat16, device=X.device)
-            hs_all = torch.empty((T + 1, B, npad, F), dtype=torch.bfloat16, device=X.device)
-            check(lib.gcrnn_pack_seq_major(_lib.BF16, _p(h0.contiguous()), _p(hs_all), B, 1, F, N, npad, None, st0), 'pack_seq')
-            check(lib.gcrnn_pack_seq_major_steps(_p(Xc), _p(xs), B, T, G, N, npad, 0, steps, 0, st0), 'pack_seq_steps')
+            xs, hs_all = _pack_leading_steps(Xc, h0, npad, F, steps)
             x_pending = Xc
         else:
             xs, hs_all = fused_pack_inputs(Xc, h0.contiguous(), graph)
     gi = gf = None
     if time_gates is not None:
         hzero = fused_h0_zero_flag(h0)
-        g = {}
-        for name in ('in', 'forget'):
-            wA_g, wB_g, bias_g, lin_w, lin_b = time_gates[name]
-            if wA_g.shape[3] != G:
-                wA_g = torch.nn.functional.pad(wA_g.detach(), (0, G - wA_g.shape[3]))
-            g[name] = fused_time_gate(xs, hs_all[:1], wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, hzero=hzero)
-        gi, gf = g['in'].contiguous(), g['forget'].contiguous()
+        gi, gf = (g.contiguous() for g in _fused_time_gates_each(xs, hs_all[:1], time_gates, graph, N, hzero, pending))
+        assert pending is None or pending.settled
     wAc, bA = _edge_composite(wA.detach(), bias.detach() if bias is not None else None, att_in[1].detach())
     wBc, bB = _edge_composite(wB.detach(), bias.detach() if bias is not None else None, att_f[1].detach())
     a_in = att_in[0].detach().float().reshape(2, F).contiguous()
@@ -1505,18 +1528,16 @@ def fused_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, time_gate
     # one workgroup per item): the x branch over all T B items, and per step the state filter with h_{t-1} as the mode's "input" operand
     wide_x = plan16 is not None and F % 32 == 0 and G % 32 == 0 and bool(lib.gcrnn_fused_filter_output_wide_supported(B, T, N, F, G, K, int(plan16['entries']), uw, 1, 0))
     wide_h = plan16 is not None and F % 32 == 0 and bool(lib.gcrnn_fused_filter_output_wide_supported(B, 1, N, F, F, K, int(plan16['entries']), uw, 1, 0))
-    p16 = (lambda: (_p(plan16['tile_slots']), _p(plan16['tile_off']), _p(plan16['ell_col4']), plan16['entries']))
     if wide_x:
         wpx = _fused_pack_weights_wide(wAc.contiguous(), wAc.new_zeros((F, 1, K, F)), uw, st)
         zx = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=X.device)
-        check(lib.gcrnn_fused_filter_output_wide_bf16(_p(xs), _p(wpx), _p(bA.contiguous() if bA is not None else None), _p(zx), *p16(), B, T, N, F, G, K, _p(x_pending), st),
-              'fused_filter_output_wide')
+        check(lib.gcrnn_fused_filter_output_wide_bf16(_p(xs), _p(wpx), _p(bA.contiguous() if bA is not None else None), _p(zx),
+                                                      *_wide_graph_args(plan16), B, T, N, F, G, K, _p(x_pending), st), 'fused_filter_output_wide')
     else:
         assert x_pending is None      # (the partial layout above was sized by the same query)
         zx = fused_filter_output(xs, wAc, bA, graph, K, N)                  # [T][B][NPad][F]
     gx = fused_edge_attention(zx, a_in, graph, out=zx, N=N, negative_slope=negative_slope)      # in place: every workgroup reads its item first
-    if Kst < K:
-        wBc = torch.cat([wBc, wBc.new_zeros(F, 1, K - Kst, F)], dim=2)
+    wBc = _pad_tap_count(wBc, K)
     bB32 = bB.contiguous() if bB is not None else None
     if wide_h:
         wpBw = _fused_pack_weights_wide(wBc.contiguous(), wBc.new_zeros((F, 1, K, F)), uw, st)      # the state taps as the "input" taps of [0 | h_{t-1}]
@@ -1527,7 +1548,7 @@ def fused_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, time_gate
     ga = _fused_graph_args(plan16 or plan)
     for t in range(T):
         if wide_h:
-            check(lib.gcrnn_fused_filter_output_wide_bf16(_p(hs_all[t]), _p(wpBw), _p(bB32), _p(zh), *p16(), B, 1, N, F, F, K, None, st), 'fused_filter_output_wide')
+            check(lib.gcrnn_fused_filter_output_wide_bf16(_p(hs_all[t]), _p(wpBw), _p(bB32), _p(zh), *_wide_graph_args(plan16), B, 1, N, F, F, K, None, st), 'fused_filter_output_wide')
         else:
             check(lib.gcrnn_fused_filter_output_bf16(_p(hs_all[t]), None, _p(wpB), _p(bB32), _p(zh), *ga, B, 1, N, F, 0, K, uw, 1 if plan16 else 0, st),
                   'fused_filter_output')
@@ -1597,7 +1618,7 @@ class _FusedEdgeCell(torch.autograd.Function):
         gfc = gf.detach().float().contiguous() if gf is not None else None
         zx = fused_filter_output(xs, wAc, bA, graph, K, N)
         gx = fused_edge_attention(zx, a_in, graph, N=N, negative_slope=slope)
-        wBk = wBc if Kst == K else torch.cat([wBc, wBc.new_zeros(F, 1, K - Kst, F)], dim=2)
+        wBk = _pad_tap_count(wBc, K)
         wpB = _fused_pack_state_taps(wBk, K, st)
         bB32 = bB.contiguous() if bB is not None else None
         H = torch.empty((B, T, F, N), dtype=torch.bfloat16, device=X.device)
@@ -1632,10 +1653,10 @@ class _FusedEdgeCell(torch.autograd.Function):
         a_f = mix_f.detach().float().reshape(2, F).contiguous()
         dH = dH.to(torch.bfloat16).contiguous()
         dHs, dHu = fused_pack_upstream(dH, graph, K)          # uniform graphs: only the last two steps; the chain launches lay out the rest
-        wBt = wBk[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)                  # transposed composite taps [F_in][1][K][F_out]
+        wBt = _transposed_taps(wBk)                                                 # transposed composite taps [F_in][1][K][F_out]
         wpT = _fused_pack_state_taps(wBt, K, st)
         aplan = graph.fused_plan(adjoint=True)
-        aplan16 = None if os.environ.get('GCRNN_NO_IMG16') else graph.fused_plan_img16(adjoint=True)
+        aplan16 = _adjoint_plan16(graph)
         aga = _fused_graph_args(aplan16 or aplan)
         auw = aplan.get('uniform_w', 0.0)
         nnz = graph.edge_plan()['nnz']
@@ -1697,14 +1718,14 @@ def fused_edge_cell_train(X, h0, wA, wB, bias, graph, att_in, att_f, time_gates=
     require_device(X, h0, wA, wB, bias)
     with torch.no_grad():
         if time_gates is not None:
-            xs, hs_all = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
+            xs, hs_all, pending = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
         else:
             xs, hs_all = fused_pack_inputs(X, h0, graph)
         hzero = fused_h0_zero_flag(h0)
     gi = gf = None
     if time_gates is not None:
-        gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, time_gates, graph, hzero)
-        assert getattr(xs, '_pending_user', None) is None
+        gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, time_gates, graph, hzero, pending=pending)
+        assert pending is None or pending.settled
     return _FusedEdgeCell.apply(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, graph, xs, hs_all, float(negative_slope))
 
 
@@ -1748,8 +1769,8 @@ def time_fused_x3_kernel(X, h0, wA, wB, bias, graph, reps=3):
     torch.cuda.synchronize()
     e0.record()
     for _ in range(reps):
-        check(lib.gcrnn_fused_forward_x3(_p(xs3), _p(h03), _p(hs3), _p(wp3), _p(b32), _p(plan['tile_slots']), _p(plan['tile_off']),
-                                         _p(plan['ell_col4']), plan['entries'], B, T, N, F, G, K, plan['uniform_w'], _p(H), 0, _p(plan.get('rank1_x3')), st),
+        check(lib.gcrnn_fused_forward_x3(_p(xs3), _p(h03), _p(hs3), _p(wp3), _p(b32), *_wide_graph_args(plan),
+                                         B, T, N, F, G, K, plan['uniform_w'], _p(H), 0, _p(plan.get('rank1_x3')), st),
               'fused_forward_x3')
     e1.record()
     torch.cuda.synchronize()
@@ -1782,8 +1803,8 @@ def fused_cell_forward_x3(X, h0, wA, wB, bias, graph, last_only=False, keep=Fals
     check(lib.gcrnn_fused_pack_weights_x3(_p(wAc), _p(wBc), _p(wp3), F, G, Kin, Kst, st), 'pack_weights_x3')
     b32 = bias.detach().float().contiguous().view(-1) if bias is not None else None
     H = torch.empty((B, 1 if last_only else T, F, N), dtype=torch.float32, device=dev)
-    check(lib.gcrnn_fused_forward_x3(_p(xs3), _p(h03), _p(hs3), _p(wp3), _p(b32), _p(plan['tile_slots']), _p(plan['tile_off']),
-                                     _p(plan['ell_col4']), plan['entries'], B, T, N, F, G, K, plan['uniform_w'], _p(H),
+    check(lib.gcrnn_fused_forward_x3(_p(xs3), _p(h03), _p(hs3), _p(wp3), _p(b32), *_wide_graph_args(plan),
+                                     B, T, N, F, G, K, plan['uniform_w'], _p(H),
                                      int(last_only), _p(plan.get('rank1_x3')), st), 'fused_forward_x3')
     if keep:
         return H, hs3, Xc
@@ -1834,22 +1855,18 @@ class _FusedCellX3(torch.autograd.Function):
         dHc = dH.float().contiguous()
         dH3 = torch.empty((T, 3, B, npad, F), dtype=torch.bfloat16, device=dev)
         check(lib.gcrnn_pack_seq_major_x3(_p(dHc), _p(dH3), B, T, F, N, npad, st), 'pack_seq_x3')
-        wBk = wB.detach().float()
-        if Kst < K:
-            wBk = torch.cat([wBk, wBk.new_zeros(F, 1, K - Kst, F)], dim=2)
-        wBt = wBk[:, 0].permute(2, 1, 0).contiguous()                       # [F_in][K][F_out]: transposed taps
-        wp3T = torch.empty((3 * (F // 16) * K * (F // 32) * 64 * 8,), dtype=torch.bfloat16, device=dev)
-        check(lib.gcrnn_fused_pack_weights_x3(_p(wBt), _p(wBt), _p(wp3T), F, 0, K, K, st), 'pack_weights_x3')
+        wBk = _pad_tap_count(wB.detach().float(), K)
+        wp3T = _pack_state_taps_x3(wBk[:, 0].permute(2, 1, 0).contiguous(), K, st)      # [F_in][K][F_out]: transposed taps
         dpre3 = torch.empty((T, 3, B, npad, F), dtype=torch.bfloat16, device=dev)
         dh03 = torch.empty((3, B, npad, F), dtype=torch.bfloat16, device=dev) if ctx.needs_input_grad[1] else None
-        check(lib.gcrnn_fused_backward_data_x3(_p(dH3), _p(hs3), _p(dpre3), _p(dh03), _p(wp3T), _p(plan['tile_slots']), _p(plan['tile_off']),
-                                               _p(plan['ell_col4']), plan['entries'], B, T, N, F, K, plan['uniform_w'], _p(plan.get('rank1_x3')), st), 'fused_backward_data_x3')
+        check(lib.gcrnn_fused_backward_data_x3(_p(dH3), _p(hs3), _p(dpre3), _p(dh03), _p(wp3T), *_wide_graph_args(plan),
+                                               B, T, N, F, K, plan['uniform_w'], _p(plan.get('rank1_x3')), st), 'fused_backward_data_x3')
         slots = int(lib.gcrnn_fused_wgrad_slots(T * B, F))
         dWp = torch.zeros((slots, F, K, F + Gp), dtype=torch.float32, device=dev)
         dbp = torch.zeros((slots, F), dtype=torch.float32, device=dev)
         h0c = h0.detach().float().contiguous()
-        check(lib.gcrnn_fused_backward_weight_f32(_p(dpre3), _p(Xp), _p(H), _p(h0c), _p(dWp), _p(dbp), _p(plan['tile_slots']), _p(plan['tile_off']),
-                                                  _p(plan['ell_col4']), plan['entries'], B, T, N, F, Gp, K, plan['uniform_w'], _p(plan.get('rank1_x3')), st), 'fused_backward_weight_f32')
+        check(lib.gcrnn_fused_backward_weight_f32(_p(dpre3), _p(Xp), _p(H), _p(h0c), _p(dWp), _p(dbp), *_wide_graph_args(plan),
+                                                  B, T, N, F, Gp, K, plan['uniform_w'], _p(plan.get('rank1_x3')), st), 'fused_backward_weight_f32')
         dW = dWp.sum(dim=0)                                                 # fixed order over the slots: bit-reproducible
         G = ctx.G
         gA = dW[:, :Kin, F:F + G].unsqueeze(1).to(wA.dtype) if ctx.needs_input_grad[2] else None
@@ -1865,6 +1882,14 @@ def fused_cell_train_x3(X, h0, wA, wB, bias, graph):
     """Training forward of the un-gated cell at fp32 accuracy on the fused kernels (fp32 tensors and parameters)."""
     require_device(X, h0, wA, wB, bias)
     return _FusedCellX3.apply(X, h0, wA, wB, bias, graph)
+
+
+def _pack_state_taps_x3(w, K, st):
+    """The x3 pack (three bf16 planes per tap) of a state-only operand: w [F][1][K][F] or [F][K][F], fp32 and contiguous."""
+    F = w.shape[0]
+    wp = torch.empty((3 * (F // 16) * K * (F // 32) * 64 * 8,), dtype=torch.bfloat16, device=w.device)
+    check(lib.gcrnn_fused_pack_weights_x3(_p(w), _p(w), _p(wp), F, 0, K, K, st), 'pack_weights_x3')
+    return wp
 
 
 def _x3_planes_to_f32(p3):
@@ -1901,7 +1926,7 @@ def _x3_time_gated_forward(X, h0, wA, wB, bias, graph, gates, keep=False, last_o
     # h0 == 0 (every training loop of the reference, train_rnn.py:256): the gate cells skip the state operand. A host-side read, so not under
     # stream capture (a captured step takes the general form: same results)
     hzero = False if torch.cuda.is_current_stream_capturing() else not bool(h0c.any())
-    gargs = (_p(plan['tile_slots']), _p(plan['tile_off']), _p(plan['ell_col4']), plan['entries'])
+    gargs = _wide_graph_args(plan)
     xs3 = torch.empty((T, 3, B, npad, Gp), dtype=torch.bfloat16, device=dev)
     check(lib.gcrnn_pack_seq_major_x3(_p(Xp), _p(xs3), B, T, Gp, N, npad, st), 'pack_seq_x3')
     h03 = torch.empty((1, 3, B, npad, F), dtype=torch.bfloat16, device=dev)
@@ -1975,7 +2000,7 @@ def fused_node_cell_forward_x3(X, h0, wA, wB, bias, graph, node_gates, time_gate
     Xc = X.detach().float().contiguous()
     h0c = h0.detach().float().contiguous()
     hzero = False if torch.cuda.is_current_stream_capturing() else not bool(h0c.any())
-    gargs = (_p(plan['tile_slots']), _p(plan['tile_off']), _p(plan['ell_col4']), plan['entries'])
+    gargs = _wide_graph_args(plan)
     r1 = _p(plan.get('rank1_x3'))
     xs3 = torch.empty((T, 3, B, npad, G), dtype=torch.bfloat16, device=dev)
     check(lib.gcrnn_pack_seq_major_x3(_p(Xc), _p(xs3), B, T, G, N, npad, st), 'pack_seq_x3')
@@ -2049,15 +2074,8 @@ def fused_node_cell_forward_x3(X, h0, wA, wB, bias, graph, node_gates, time_gate
             else:
                 nf = nf * tgv
 
-    def state_taps(w, k):      # F x 1 x k x F taps -> the x3 pack of a state-only operand with K taps
-        wk = w.detach().float()
-        if k < K:
-            wk = torch.cat([wk, wk.new_zeros(F, 1, K - k, F)], dim=2)
-        wk = wk.contiguous()
-        wp = torch.empty((3 * (F // 16) * K * (F // 32) * 64 * 8,), dtype=torch.bfloat16, device=dev)
-        check(lib.gcrnn_fused_pack_weights_x3(_p(wk), _p(wk), _p(wp), F, 0, K, K, st), 'pack_weights_x3')
-        return wp
-    wp3A, wp3B = state_taps(wA, Kin), state_taps(wB, Kst)
+    # F x 1 x k x F taps -> the x3 pack of a state-only operand with K taps
+    wp3A, wp3B = (_pack_state_taps_x3(_pad_tap_count(w.detach().float(), K).contiguous(), K, st) for w in (wA, wB))
     b32 = bias.detach().float().contiguous().view(-1) if bias is not None else None
     ya3 = torch.empty((3, B, npad, F), dtype=torch.bfloat16, device=dev)
     yb3 = torch.empty((3, B, npad, F), dtype=torch.bfloat16, device=dev)
@@ -2088,7 +2106,7 @@ def fused_edge_cell_forward_x3(X, h0, wA, wB, bias, graph, att_in, att_f, time_g
     npad, st, dev = plan['npad'], _stream(), X.device
     Xc = X.detach().float().contiguous()
     h0c = h0.detach().float().contiguous()
-    gargs = (_p(plan['tile_slots']), _p(plan['tile_off']), _p(plan['ell_col4']), plan['entries'])
+    gargs = _wide_graph_args(plan)
     r1 = _p(plan.get('rank1_x3'))
     xs3 = torch.empty((T, 3, B, npad, G), dtype=torch.bfloat16, device=dev)
     check(lib.gcrnn_pack_seq_major_x3(_p(Xc), _p(xs3), B, T, G, N, npad, st), 'pack_seq_x3')
@@ -2116,15 +2134,7 @@ def fused_edge_cell_forward_x3(X, h0, wA, wB, bias, graph, att_in, att_f, time_g
             del c
         gi, gf = gv
 
-    def state_taps(w, k):
-        wk = w.detach().float()
-        if k < K:
-            wk = torch.cat([wk, wk.new_zeros(F, 1, K - k, F)], dim=2)
-        wk = wk.contiguous()
-        wp = torch.empty((3 * (F // 16) * K * (F // 32) * 64 * 8,), dtype=torch.bfloat16, device=dev)
-        check(lib.gcrnn_fused_pack_weights_x3(_p(wk), _p(wk), _p(wp), F, 0, K, K, st), 'pack_weights_x3')
-        return wp
-    wp3A, wp3B = state_taps(wA, Kin), state_taps(wB, Kst)
+    wp3A, wp3B = (_pack_state_taps_x3(_pad_tap_count(w.detach().float(), K).contiguous(), K, st) for w in (wA, wB))
     bvec = bias.detach().float().view(1, 1, F) if bias is not None else None
     y3 = torch.empty((3, B, npad, F), dtype=torch.bfloat16, device=dev)
 
@@ -2183,8 +2193,8 @@ class _FusedTimeCellX3(torch.autograd.Function):
         K = max(Kin, Kst)
         plan, pa = graph.fused_plan_x3(), graph.fused_plan_x3(adjoint=True)
         npad, st, dev = pa['npad'], _stream(), Xp.device
-        gargs = (_p(plan['tile_slots']), _p(plan['tile_off']), _p(plan['ell_col4']), plan['entries'])
-        aargs = (_p(pa['tile_slots']), _p(pa['tile_off']), _p(pa['ell_col4']), pa['entries'])
+        gargs = _wide_graph_args(plan)
+        aargs = _wide_graph_args(pa)
         nparts = (F // 16) * 8
         # ---- the gated data chain, d gf read off it ----
         dHc = dH.float().contiguous()
@@ -2192,12 +2202,8 @@ class _FusedTimeCellX3(torch.autograd.Function):
         check(lib.gcrnn_pack_seq_major_x3(_p(dHc), _p(dH3), B, T, F, N, npad, st), 'pack_seq_x3')
         h03 = torch.empty((1, 3, B, npad, F), dtype=torch.bfloat16, device=dev)
         check(lib.gcrnn_pack_seq_major_x3(_p(h0c), _p(h03), B, 1, F, N, npad, st), 'pack_seq_x3')
-        wBk = wB.detach().float()
-        if Kst < K:
-            wBk = torch.cat([wBk, wBk.new_zeros(F, 1, K - Kst, F)], dim=2)
-        wBt = wBk[:, 0].permute(2, 1, 0).contiguous()
-        wp3T = torch.empty((3 * (F // 16) * K * (F // 32) * 64 * 8,), dtype=torch.bfloat16, device=dev)
-        check(lib.gcrnn_fused_pack_weights_x3(_p(wBt), _p(wBt), _p(wp3T), F, 0, K, K, st), 'pack_weights_x3')
+        wBk = _pad_tap_count(wB.detach().float(), K)
+        wp3T = _pack_state_taps_x3(wBk[:, 0].permute(2, 1, 0).contiguous(), K, st)
         dpre3 = torch.empty((T, 3, B, npad, F), dtype=torch.bfloat16, device=dev)
         dh03 = torch.empty((3, B, npad, F), dtype=torch.bfloat16, device=dev)
         parts = torch.empty((T, B, nparts), dtype=torch.float32, device=dev)
@@ -2210,8 +2216,7 @@ class _FusedTimeCellX3(torch.autograd.Function):
         wAk = wA.detach().float()[:, 0]                                                              # [F][Kin][G]
         wAsq = torch.zeros((F, K, F), dtype=torch.float32, device=dev)
         wAsq[:, :Kin, :wAk.shape[2]] = wAk
-        wp3A = torch.empty((3 * (F // 16) * K * (F // 32) * 64 * 8,), dtype=torch.bfloat16, device=dev)
-        check(lib.gcrnn_fused_pack_weights_x3(_p(wAsq), _p(wAsq), _p(wp3A), F, 0, K, K, st), 'pack_weights_x3')
+        wp3A = _pack_state_taps_x3(wAsq, K, st)
         z3 = ctx.xu3
         ctx.xu3 = None
         if z3 is None:
@@ -2316,37 +2321,29 @@ def fused_backward_data(dHs, hs, wB, graph, want_dh0=True, gf=None, h0s=None, bi
     K = wB.shape[2]
     plan = graph.fused_plan(adjoint=True)
     st = _stream()
-    wBt = wB.detach()[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)      # [F_in][1][K][F_out]: transposed taps
+    wBt = _transposed_taps(wB)                                              # [F_in][1][K][F_out]
     dpre = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=hs.device)
     dh0 = torch.empty((B, npad, F), dtype=torch.bfloat16, device=hs.device) if want_dh0 else None
-    import os
-    plan16 = None if os.environ.get('GCRNN_NO_IMG16') else graph.fused_plan_img16(adjoint=True)      # bf16 hop image, matrix-core sums (uniform graphs)
-    pw = plan16
-    if pw is None and not os.environ.get('GCRNN_NO_IMG16'):
-        pw = graph.fused_plan_rank1(adjoint=True)        # rank-1-weighted graph (normalised adjacency): the adjoint plan of its pattern + the swapped factors
+    plan16 = _adjoint_plan16(graph)                      # bf16 hop image, matrix-core sums (uniform graphs)
+    pw = plan16 if plan16 is not None else _adjoint_plan16(graph, rank1=True)
     if pw is not None and F % 32 == 0 and not os.environ.get('GCRNN_NO_WIDE_CHAIN') and lib.gcrnn_fused_backward_data_wide_supported(
             B, T, graph.N, F, K, int(pw['entries']), float(pw.get('uniform_w', 0.0)), 3 if pw.get('rank1') else 1, 1 if dH_user is not None else 0):
         plan16 = pw
         # the whole chain (seed, T - 1 steps, d h0 / the forget gate's step 0) as ONE launch of the wide sequence-resident kernel
         wpw = _fused_pack_weights_wide(wBt.new_zeros((F, 1, K, 0)), wBt, plan16['uniform_w'], st)
         parts = torch.empty((T * B, (F // 32) * int(lib.gcrnn_fused_step_waves())), dtype=torch.float32, device=hs.device) if h0s is not None else None
-        check(lib.gcrnn_fused_backward_data_wide_bf16(_p(dHs), _p(hs), _p(dpre), _p(dh0), _p(wpw), _p(plan16['tile_slots']), _p(plan16['tile_off']),
-                                                      _p(plan16['ell_col4']), plan16['entries'], B, T, graph.N, F, K, _p(gf), _p(h0s), _p(parts),
+        check(lib.gcrnn_fused_backward_data_wide_bf16(_p(dHs), _p(hs), _p(dpre), _p(dh0), _p(wpw), *_wide_graph_args(plan16),
+                                                      B, T, graph.N, F, K, _p(gf), _p(h0s), _p(parts),
                                                       _p(dH_user), _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st), 'fused_backward_data_wide')
-        if h0s is None:
-            return dpre, dh0
-        dgf = parts.sum(dim=1).view(T, B)
-        if bias is not None:
-            dgf = dgf + dpre.sum(dim=2, dtype=torch.float32) @ bias.detach().float().view(-1)
-        return dpre, dh0, dgf
-    wpack = _fused_pack_state_taps(wBt, K, st)
-    parts = None
-    if h0s is not None:
-        parts = torch.empty((T * B, (F // 16) * int(lib.gcrnn_fused_step_waves())), dtype=torch.float32, device=hs.device)
-    check(lib.gcrnn_fused_backward_data_bf16(_p(dHs), _p(hs), _p(dpre), _p(dh0), _p(wpack), *_fused_graph_args(plan16 or plan),
-                                             B, T, graph.N, F, K, _p(gf), _p(h0s), _p(parts), plan.get('uniform_w', 0.0), _p(dH_user),
-                                             1 if plan16 else 0, st),
-          'fused_backward_data')
+    else:
+        wpack = _fused_pack_state_taps(wBt, K, st)
+        parts = None
+        if h0s is not None:
+            parts = torch.empty((T * B, (F // 16) * int(lib.gcrnn_fused_step_waves())), dtype=torch.float32, device=hs.device)
+        check(lib.gcrnn_fused_backward_data_bf16(_p(dHs), _p(hs), _p(dpre), _p(dh0), _p(wpack), *_fused_graph_args(plan16 or plan),
+                                                 B, T, graph.N, F, K, _p(gf), _p(h0s), _p(parts), plan.get('uniform_w', 0.0), _p(dH_user),
+                                                 1 if plan16 else 0, st),
+              'fused_backward_data')
     if h0s is None:
         return dpre, dh0
     dgf = parts.sum(dim=1).view(T, B)
@@ -2381,9 +2378,9 @@ def fused_backward_weight(dpre, X, H, h0, graph, F, G, K, want_bias=False, gi=No
     Xc, h0c = X.contiguous(), h0.contiguous()
     Hc = H.contiguous() if H is not None else None
     uw = 0.0 if os.environ.get('GCRNN_WGRAD_NO_UNIFORM') else plan.get('uniform_w', 0.0)      # env: A/B switch
-    plan16 = None if (uw == 0.0 or os.environ.get('GCRNN_NO_IMG16')) else graph.fused_plan_img16(adjoint=True)      # bf16 hop image
-    if plan16 is None and uw == 0.0 and not os.environ.get('GCRNN_NO_IMG16') and not os.environ.get('GCRNN_WGRAD_NO_UNIFORM'):
-        plan16 = graph.fused_plan_rank1(adjoint=True)    # rank-1-weighted graph: the adjoint plan of its 0/1 pattern + the factors of S^T (kernel variant R1)
+    plan16 = None if uw == 0.0 else _adjoint_plan16(graph)      # bf16 hop image
+    if plan16 is None and uw == 0.0 and not os.environ.get('GCRNN_WGRAD_NO_UNIFORM'):
+        plan16 = _adjoint_plan16(graph, rank1=True)      # rank-1-weighted graph: kernel variant R1
         if plan16 is not None:
             uw = 1.0
     pl = plan16 or plan
@@ -2419,8 +2416,7 @@ def fused_gate_grad(zs, dpre, w, bias, graph, K):
     else:
         wd = w.detach()
         wz = wd.new_zeros((F, 1, K, F))
-        if wd.shape[2] < K:
-            wd = torch.cat([wd, wd.new_zeros(F, 1, K - wd.shape[2], Cin)], dim=2)
+        wd = _pad_tap_count(wd, K)
         wp = _fused_pack_weights(wd, wz, st)
         zero_h = torch.zeros((1, npad, F), dtype=torch.bfloat16, device=dpre.device)
         check(lib.gcrnn_fused_gate_grad_bf16(_p(zero_h), _p(zs), _p(dpre), _p(wp), _p(b32), _p(parts), *_fused_graph_args(plan16 or plan),
@@ -2448,9 +2444,9 @@ class _FusedTimeGate(torch.autograd.Function):
                from h0 = 0 and never ask for either, train_rnn.py:247-276)."""
 
     @staticmethod
-    def forward(ctx, xs, h0s, X, h0, wA_g, wB_g, bias_g, lin_w, lin_b, graph, hzero):
+    def forward(ctx, xs, h0s, X, h0, wA_g, wB_g, bias_g, lin_w, lin_b, graph, hzero, pending=None):
         N = X.shape[3]
-        gate, cs, gw = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, store_states=True, hzero=hzero)
+        gate, cs, gw = fused_time_gate(xs, h0s, wA_g, wB_g, bias_g, lin_w, lin_b, graph, N, store_states=True, hzero=hzero, pending=pending)
         ctx.save_for_backward(X, h0, wA_g, wB_g, bias_g, lin_w, lin_b, gate, cs, gw, hzero)
         ctx.graph = graph
         return gate
@@ -2467,8 +2463,8 @@ class _FusedTimeGate(torch.autograd.Function):
             raise GcrnnError('the fused time gate produces gradients w.r.t. X or h0 only for G == F')
         res = _time_gate_backward(X, h0, wA_g, wB_g, bias_g, lin_w, lin_b, gate, cs, gw, hzero, ctx.graph, dgate, ctx.needs_input_grad[4:9], wx, wh)
         if wx or wh:
-            return (None, None, res[0], res[1]) + res[2:] + (None, None)
-        return (None, None, None, None) + res + (None, None)
+            return (None, None, res[0], res[1]) + res[2:] + (None, None, None)
+        return (None, None, None, None) + res + (None, None, None)
 
 
 def _time_gate_input_grads(X, h0, wA_g, wB_g, dpre_g, graph, want_x, want_h0):
@@ -2483,20 +2479,14 @@ def _time_gate_input_grads(X, h0, wA_g, wB_g, dpre_g, graph, want_x, want_h0):
     st = _stream()
     gX = gh0 = None
     if want_x:
-        wAk = wA_g if Kin == K else torch.cat([wA_g, wA_g.new_zeros(F, 1, K - Kin, G)], dim=2)
-        wAt = wAk.detach()[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)       # [G][1][K][F]: transposed taps
+        wAt = _transposed_taps(_pad_tap_count(wA_g, K))                           # [G][1][K][F]
         dxs = fused_filter_output(dpre_g, wAt, None, graph, K, N, adjoint=True)   # [T][B][NPad][G] bf16
-        gX = torch.empty((B, T, G, N), dtype=torch.bfloat16, device=X.device)
-        check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(dxs), _p(gX), B, T, G, N, npad, None, st), 'unpack_seq')
-        gX = gX.to(X.dtype)
+        gX = _unpack_grad(dxs, B, T, G, N, st).to(X.dtype)
     if want_h0:
-        wBk = wB_g if Kst == K else torch.cat([wB_g, wB_g.new_zeros(F, 1, K - Kst, F)], dim=2)
-        wBt = wBk.detach()[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)
+        wBt = _transposed_taps(_pad_tap_count(wB_g, K))
         dhs = fused_filter_output(dpre_g, wBt, None, graph, K, N, adjoint=True)   # every item's contribution to its sequence's h0
         dh = dhs.float().sum(dim=0).to(torch.bfloat16).unsqueeze(0).contiguous()  # [1][B][NPad][F]: fp32 sum over the T items of a sequence
-        gh0 = torch.empty((B, 1, F, N), dtype=torch.bfloat16, device=X.device)
-        check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(dh), _p(gh0), B, 1, F, N, npad, None, st), 'unpack_seq')
-        gh0 = gh0.view(B, F, N).to(h0.dtype)
+        gh0 = _unpack_grad(dh, B, 1, F, N, st).view(B, F, N).to(h0.dtype)
     return gX, gh0
 
 
@@ -2533,10 +2523,10 @@ class _FusedTimeGatePair(torch.autograd.Function):
     (fused_time_gate_pair: the two sub-cells as one cell of 2 F outputs; states of both stored), backward = _FusedTimeGate's, once per gate."""
 
     @staticmethod
-    def forward(ctx, xs, h0s, X, h0, wA_i, wB_i, b_i, lw_i, lb_i, wA_f, wB_f, b_f, lw_f, lb_f, graph, hzero):
+    def forward(ctx, xs, h0s, X, h0, wA_i, wB_i, b_i, lw_i, lb_i, wA_f, wB_f, b_f, lw_f, lb_f, graph, hzero, pending=None):
         N = X.shape[3]
         gi, gf, (cs_i, gw_i), (cs_f, gw_f) = fused_time_gate_pair(xs, h0s, (wA_i, wB_i, b_i, lw_i, lb_i), (wA_f, wB_f, b_f, lw_f, lb_f), graph, N,
-                                                                  store_states=True, hzero=hzero)
+                                                                  store_states=True, hzero=hzero, pending=pending)
         ctx.save_for_backward(X, h0, wA_i, wB_i, b_i, lw_i, lb_i, wA_f, wB_f, b_f, lw_f, lb_f, gi, gf, cs_i, gw_i, cs_f, gw_f, hzero)
         ctx.graph = graph
         return gi, gf
@@ -2560,12 +2550,12 @@ class _FusedTimeGatePair(torch.autograd.Function):
             gX = (g_in[0] + g_f[0]) if wx else None
             gh0 = (g_in[1] + g_f[1]) if wh else None
             g_in, g_f = g_in[2:], g_f[2:]
-        return (None, None, gX, gh0) + g_in + g_f + (None, None)
+        return (None, None, gX, gh0) + g_in + g_f + (None, None, None)
 
 
-def fused_train_time_gates(xs, h0s, X, h0, gates, graph, hzero):
+def fused_train_time_gates(xs, h0s, X, h0, gates, graph, hzero, pending=None):
     """The two differentiable time gates [T][B] of a training step: ONE pre-pass launch for the pair where the wide kernel takes the problem
-    (uniform-weight graph, a batch that fills the chip), else one launch per gate."""
+    (uniform-weight graph, a batch that fills the chip), else one launch per gate. pending: the _PendingLayout of xs; the first launch settles it."""
     T, B, npad, G = xs.shape
     N = X.shape[3]
     gin, gfo = gates['in'], gates['forget']
@@ -2573,10 +2563,10 @@ def fused_train_time_gates(xs, h0s, X, h0, gates, graph, hzero):
     K = max(gin[0].shape[2], gin[1].shape[2])
     pair16 = None
     if gin[0].shape == gfo[0].shape and gin[1].shape == gfo[1].shape and gin[0].shape[3] == G and not os.environ.get('GCRNN_NO_GATE_PAIR_TRAIN'):
-        pair16, _ = fused_gate_pair_plan(graph, B, T, N, F, G, K, getattr(xs, '_pending_user', None) is not None)
+        pair16, _ = fused_gate_pair_plan(graph, B, T, N, F, G, K, pending is not None and not pending.settled)
     if pair16 is not None:
-        return _FusedTimeGatePair.apply(xs, h0s, X, h0, *gin, *gfo, graph, hzero)
-    gi = _FusedTimeGate.apply(xs, h0s, X, h0, *gin, graph, hzero)
+        return _FusedTimeGatePair.apply(xs, h0s, X, h0, *gin, *gfo, graph, hzero, pending)
+    gi = _FusedTimeGate.apply(xs, h0s, X, h0, *gin, graph, hzero, pending)
     gf = _FusedTimeGate.apply(xs, h0s, X, h0, *gfo, graph, hzero)
     return gi, gf
 
@@ -2619,7 +2609,7 @@ class _FusedCell(torch.autograd.Function):
             gi, gf = gi.detach().float().contiguous(), gf.detach().float().contiguous()
         dH = dH.to(torch.bfloat16).contiguous()
         dHs, dHu = fused_pack_upstream(dH, graph, K)
-        wBk = wB if Kst == K else torch.cat([wB, wB.new_zeros(F, 1, K - Kst, F)], dim=2)
+        wBk = _pad_tap_count(wB, K)
         dgf = None
         if gated and ctx.needs_input_grad[6]:
             dpre, dh0s, dgf = fused_backward_data(dHs, hs, wBk, graph, want_dh0=ctx.needs_input_grad[1], gf=gf,
@@ -2638,17 +2628,13 @@ class _FusedCell(torch.autograd.Function):
             dgi = fused_gate_grad(xsq, dpre, wA, bias, graph, K)
         gh0 = None
         if ctx.needs_input_grad[1]:
-            gh0 = torch.empty((B, 1, F, N), dtype=torch.bfloat16, device=X.device)
-            check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(dh0s), _p(gh0), B, 1, F, N, npad, None, st), 'unpack_seq')
-            gh0 = gh0.view(B, F, N).to(h0.dtype)
+            gh0 = _unpack_grad(dh0s, B, 1, F, N, st).view(B, F, N).to(h0.dtype)
         gX = None
         if ctx.needs_input_grad[0]:
             # dX_t = gi_t sum_k (dpre_t A_k) shifted k times by S^T: the input filter's adjoint, every item in one launch
-            wAk = wA if Kin == K else torch.cat([wA, wA.new_zeros(F, 1, K - Kin, G)], dim=2)
-            wAt = wAk.detach()[:, 0].permute(2, 1, 0).contiguous().unsqueeze(1)       # [G][1][K][F]: transposed taps
+            wAt = _transposed_taps(_pad_tap_count(wA, K))                             # [G][1][K][F]
             dxs = fused_filter_output(dpre, wAt, None, graph, K, N, adjoint=True)     # [T][B][NPad][G] bf16
-            gX = torch.empty((B, T, G, N), dtype=torch.bfloat16, device=X.device)
-            check(lib.gcrnn_unpack_seq_major(_lib.BF16, _p(dxs), _p(gX), B, T, G, N, npad, None, st), 'unpack_seq')
+            gX = _unpack_grad(dxs, B, T, G, N, st)
             if gated:
                 gX = gX * gi.t().reshape(B, T, 1, 1).to(gX.dtype)
             gX = gX.to(X.dtype)
@@ -2668,10 +2654,10 @@ def fused_cell_train(X, h0, wA, wB, bias, graph, gates=None):
     if gates is None:
         return _FusedCell.apply(X, h0, wA, wB, bias, None, None, graph, None, None)
     with torch.no_grad():
-        xs, hs_all = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
+        xs, hs_all, pending = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
         hzero = fused_h0_zero_flag(h0)
-    gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, gates, graph, hzero)
-    assert getattr(xs, '_pending_user', None) is None          # (the first pre-pass laid out the rest of X)
+    gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, gates, graph, hzero, pending=pending)
+    assert pending is None or pending.settled                   # (the first pre-pass laid out the rest of X)
     return _FusedCell.apply(X, h0, wA, wB, bias, gi, gf, graph, xs, hs_all)
 
 

@@ -1018,7 +1018,7 @@ def test_pending_layout_is_settled_when_another_prepass_runs_first(gating, monke
     """fused_pack_inputs_gated leaves the layout of X to the first gate pre-pass and sizes the laid-out head for the pre-pass it expects
     (the wide kernel's pair pre-pass). Where another one runs first -- node-gated TRAINING stores the gate cells' states through the
     16-feature kernel's per-gate pre-pass, which does not lay out at B = 100 -- the rest of X is laid out by the plain pack
-    (ops._pending_layout_for) instead of failing (examples/kstep_prediction.py --nodes 1000 --sparse --dtype bf16: the drivers' batch,
+    (ops._PendingLayout.settle) instead of failing (examples/kstep_prediction.py --nodes 1000 --sparse --dtype bf16: the drivers' batch,
     kStepPredGRNNs.py:168, one input feature). Results equal the eager layout's (GCRNN_NO_INLINE_PACK=1) bit for bit."""
     import gated_gcrnns_amd.Utils.graphML as gml
     N, F, G, K, B, T = 1000, 64, 1, 5, 100, 8
