@@ -410,6 +410,8 @@ class GGCRNNCell(nn.Module):
                                                       self._fused_gates() if self.time_gating == True else None, last_only=True)  # noqa: E712
             if (not torch.is_grad_enabled()) and self._use_fused_edge(X, h0):
                 return self._forward_fused_edge(X, h0, last_only=True)
+            if self._use_small_edge(X, h0):
+                return self._forward_small_edge(X, h0, last_only=True)
             return self.forward(X, h0)[:, -1:]
         assert h0.shape[0] == X.shape[0]
         ops.require_device(X, h0, self.weight_A)
@@ -446,6 +448,8 @@ class GGCRNNCell(nn.Module):
             return ops.fused_edge_cell_forward_x3(X, h0, self.weight_A, self.weight_B, self.bias, self.graph,
                                                   self.input_attention.forward_node_major, self.forget_attention.forward_node_major,
                                                   self._fused_gates() if self.time_gating == True else None)  # noqa: E712
+        if self._use_small_edge(X, h0):
+            return self._forward_small_edge(X, h0)
         if self._use_small(X, h0):
             return self._forward_small(X, h0)
         if self._use_small_training(X, h0):
@@ -636,7 +640,8 @@ class GGCRNNCell(nn.Module):
         return self.weight_A.dtype == X.dtype and h0.dtype == X.dtype and \
             ops.small_training_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E)
 
-    def _forward_small(self, X, h0, train=False):
+    def _small_time_gates(self, X, h0, train=False):
+        """(gi, gf), each [T][B], of a time-gated cell on a small graph; (None, None) without time gating."""
         gi = gf = None
         if self.time_gating == True and ops.small_gates_supported(  # noqa: E712
                 self.N, self.G, self.F, self.Kin, self.Kst, X.dtype, backward=train):
@@ -655,6 +660,30 @@ class GGCRNNCell(nn.Module):
             h0n = ops.pack_node_major(h0.reshape(B, 1, self.F, self.N))
             gi = self._time_gate(self.GFL_in, self.MLP_in, Xn, h0n).reshape(X.shape[1], B)
             gf = self._time_gate(self.GFL_forget, self.MLP_forget, Xn, h0n).reshape(X.shape[1], B)
+        return gi, gf
+
+    def _use_small_edge(self, X, h0):
+        """Edge-gated cell (optionally time-gated too) on a small graph, fp32 / fp64, inference: the input branch of all steps in one
+        launch, the recurrence in a second (ops.small_edge_cell_forward). GCRNN_NO_SMALL_EDGE=1 switches back to the composed path (A/B)."""
+        if self.spatial_gating != 'edge' or self._wants_grad(X, h0) or not self._sigma_is_tanh() or os.environ.get('GCRNN_NO_SMALL_EDGE'):
+            return False
+        if self.graph is None or not self._attention_fusable():
+            return False
+        dt = X.dtype
+        if dt not in (torch.float32, torch.float64) or h0.dtype != dt or any(p.dtype != dt for p in self.parameters()):
+            return False
+        return ops.small_edge_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin, self.Kst, dt, self.E)
+
+    def _forward_small_edge(self, X, h0, last_only=False):
+        assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
+        ops.require_device(X, h0, self.weight_A)
+        gi, gf = self._small_time_gates(X, h0)
+        return ops.small_edge_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph,
+                                           (self.input_attention.mixer, self.input_attention.weight),
+                                           (self.forget_attention.mixer, self.forget_attention.weight), gi, gf, last_only=last_only)
+
+    def _forward_small(self, X, h0, train=False):
+        gi, gf = self._small_time_gates(X, h0, train)
         if self.spatial_gating == 'node':
             # node gates (graphML.py:2379-2399) from one batched pass over all t; the recurrence takes them per node,
             # multiplied by the time gates when both are on: gates [B][T][N]

@@ -2838,6 +2838,55 @@ def small_time_gates(X, h0, wA2, wB2, bias2, lw2, lb2, graph):
     return _SmallTimeGates.apply(X, h0, wA2, wB2, bias2, lw2, lb2, graph)
 
 
+# ------------------------------------------------------------------------------------------ small-graph edge-gated cell
+def small_edge_supported(N, nnz, nnz_support, G, F, Kin, Kst, dtype, E=1):
+    if E != 1 or dtype not in (torch.float32, torch.float64):
+        return False
+    return bool(lib.gcrnn_small_edge_supported(dtype_code(dtype), int(N), int(nnz), int(nnz_support), int(G), int(F), int(Kin), int(Kst)))
+
+
+def _edge_support_values(graph, dtype):
+    """(S + I)[m][n] on the attention support in the order of edge_plan()['t_edge'], in the data dtype (the plan itself carries fp32 bits)."""
+    cache = graph.__dict__.setdefault('_edge_t_vals', {})
+    if dtype not in cache:
+        cache[dtype] = graph.mask_vals[0][graph.edge_plan()['t_pos'].long()].to(dtype).contiguous()
+    return cache[dtype]
+
+
+def small_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, gf=None, last_only=False):
+    """Edge-gated cell (optionally time-gated too) on a small graph, inference: the input branch of all steps in one launch, the whole
+    recurrence in a second one with one workgroup per sequence. X: B x T x G x N, h0: B x F x N (user layout, fp32 / fp64) -> H: B x T x F x N,
+    or B x 1 x F x N (the last state) with last_only. att_in / att_f: (mixer 1 x 1 x 2F, weight 1 x 1 x F x F) of the input / forget
+    attention; gi / gf: time gates [T][B] or None."""
+    require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1])
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    dt = X.dtype
+    csr = graph.fwd[0]
+    plan = graph.edge_plan()
+    nnzs = plan['nnz']
+    for mixer, weight in (att_in, att_f):
+        assert tuple(mixer.shape) == (1, 1, 2 * F) and tuple(weight.shape) == (1, 1, F, F), 'one head, one edge feature, F -> F'
+    if not small_edge_supported(N, csr.nnz, nnzs, G, F, Kin, Kst, dt, graph.E):
+        raise GcrnnError('small_edge_cell_forward: shape outside the one-launch edge-gated kernel (small_edge_supported)')
+    H = torch.empty((B, 1 if last_only else T, F, N), dtype=dt, device=X.device)
+    Ya = torch.empty((B, T, F, N), dtype=dt, device=X.device)
+    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+    if gi is not None:
+        assert tuple(gi.shape) == (T, B) and tuple(gf.shape) == (T, B)
+        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
+    ops_in = [t.detach().contiguous() for t in (X, h0, wA, wB)]
+    atts = [t.detach().contiguous() for t in (att_in[1], att_in[0], att_f[1], att_f[0])]
+    assert all(t.dtype == dt for t in ops_in + atts) and (bvec is None or bvec.dtype == dt)
+    vals, tvals = csr.val(dt), _edge_support_values(graph, dt)
+    check(lib.gcrnn_small_edge_forward(dtype_code(dt), _p(ops_in[0]), _p(ops_in[1]), _p(ops_in[2]), _p(ops_in[3]), _p(bvec),
+                                       _p(atts[0]), _p(atts[1]), _p(atts[2]), _p(atts[3]), _p(gi), _p(gf),
+                                       _p(csr.rowptr), _p(csr.col), _p(vals), _p(plan['rowptr']), _p(plan['r_edge']),
+                                       _p(plan['t_rowptr']), _p(plan['t_edge']), _p(tvals), _p(Ya), _p(H),
+                                       B, T, N, G, F, Kin, Kst, csr.nnz, nnzs, int(bool(last_only)), _stream()), 'small_edge_forward')
+    return H
+
+
 # ------------------------------------------------------------------------------------------ per-node head
 def node_linear_supported(F, O, dtype, N=None, wdtype=None):
     if dtype == torch.bfloat16:            # bf16 activations (the fused cell's output), fp32 master or bf16 parameters

@@ -705,7 +705,25 @@ int gcrnn_small_gates_backward(int dtype, const void* X, const void* h0, const v
                                void* plb, void* pdh0, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
                                int64_t Kst, void* stream);
 
-/* ==== per-node output head =========================================================================================
+/* EDGE-gated cell of the small-graph regime (spatial_gating = 'edge', graphML.py:2411-2416 with graphAttention, graphML.py:521-627;
+ * one head, one edge feature, concatenated, ReLU), inference: h_t = tanh(gi_t att_in(A(S) x_t + b) + gf_t att_f(B(S) h_{t-1} + b)).
+ * Two launches whatever T is: the input branch of every (b, t) at once into the scratch Ya [B][T][F][N], then the recurrence with
+ * one workgroup per sequence and the state in LDS. att_*_w [F][F] (GraphAttentional.weight[0][0]), att_*_a [2 F] (mixer[0][0],
+ * a1 | a2). CSR(S^T) rowptr/col/val as gcrnn_small_forward; the attention support |S + I| > 1e-9 as row lists (s_rowptr [N+1],
+ * r_edge [nnz_support][2] int32 = {column n, unused}) and column lists (t_rowptr [N+1], t_edge [nnz_support][2] int32 =
+ * {row m, unused}, t_val [nnz_support] = (S + I)[m][n] in the data dtype, in the order of t_edge). y[:, n] is summed in the order of
+ * the column list; no atomics. A row with an empty support contributes nothing. gi / gf [T][B] or both NULL.
+ * last_only != 0: H is [B][1][F][N] and receives the last state only. dtype F32 or F64. */
+int gcrnn_small_edge_supported(int dtype, int64_t N, int64_t nnz, int64_t nnz_support, int64_t G, int64_t F, int64_t Kin,
+                               int64_t Kst);
+int gcrnn_small_edge_forward(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                             const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a, const void* gi,
+                             const void* gf, const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* s_rowptr,
+                             const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val, void* Ya,
+                             void* H, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz,
+                             int64_t nnz_support, int last_only, void* stream);
+
+/* ==== per-node output head=========================================================================================
  * mlpType = 'multipMlp' of GatedGCRNNforRegression (architectures.py:1616-1627: one Linear(F -> O) applied to every node's
  * state in a Python loop over nodes), on the user layout: h [R][F][N] -> y [R][O][N], R = B * T, F <= 64, O <= 8, F32 / F64.
  * backward: dh [R][F][N] (or NULL), pw [gcrnn_node_linear_blocks(R, N)][O][F] and pb [blocks][O] partial sums of dw / db. */
