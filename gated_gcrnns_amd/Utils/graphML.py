@@ -450,6 +450,8 @@ class GGCRNNCell(nn.Module):
                                                   self._fused_gates() if self.time_gating == True else None)  # noqa: E712
         if self._use_small_edge(X, h0):
             return self._forward_small_edge(X, h0)
+        if self._use_small_edge_training(X, h0):
+            return self._forward_small_edge(X, h0, train=True)
         if self._use_small(X, h0):
             return self._forward_small(X, h0)
         if self._use_small_training(X, h0):
@@ -665,22 +667,41 @@ class GGCRNNCell(nn.Module):
     def _use_small_edge(self, X, h0):
         """Edge-gated cell (optionally time-gated too) on a small graph, fp32 / fp64, inference: the input branch of all steps in one
         launch, the recurrence in a second (ops.small_edge_cell_forward). GCRNN_NO_SMALL_EDGE=1 switches back to the composed path (A/B)."""
-        if self.spatial_gating != 'edge' or self._wants_grad(X, h0) or not self._sigma_is_tanh() or os.environ.get('GCRNN_NO_SMALL_EDGE'):
+        if self._wants_grad(X, h0) or not self._small_edge_takes(X, h0):
+            return False
+        dt = X.dtype
+        return ops.small_edge_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin, self.Kst, dt, self.E)
+
+    def _small_edge_takes(self, X, h0):
+        """What the one-launch edge-gated kernels ask of the cell and its tensors, whatever the gradient mode (the shape is asked separately)."""
+        if self.spatial_gating != 'edge' or not self._sigma_is_tanh() or os.environ.get('GCRNN_NO_SMALL_EDGE'):
             return False
         if self.graph is None or not self._attention_fusable():
             return False
         dt = X.dtype
-        if dt not in (torch.float32, torch.float64) or h0.dtype != dt or any(p.dtype != dt for p in self.parameters()):
-            return False
-        return ops.small_edge_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin, self.Kst, dt, self.E)
+        return dt in (torch.float32, torch.float64) and h0.dtype == dt and all(p.dtype == dt for p in self.parameters())
 
-    def _forward_small_edge(self, X, h0, last_only=False):
+    def _use_small_edge_training(self, X, h0):
+        """Edge-gated cell on a small graph, gradients wanted for parameters / h0 but not for X: the forward of _use_small_edge with every
+        state kept, BPTT in two launches (ops.small_edge_cell_train). GCRNN_NO_SMALL_EDGE=1 switches this path off too."""
+        if not torch.is_grad_enabled() or X.requires_grad:
+            return False
+        if not (h0.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        if not self._small_edge_takes(X, h0):
+            return False
+        return ops.small_edge_training_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin,
+                                                 self.Kst, X.dtype, self.E)
+
+    def _forward_small_edge(self, X, h0, last_only=False, train=False):
         assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
         ops.require_device(X, h0, self.weight_A)
-        gi, gf = self._small_time_gates(X, h0)
-        return ops.small_edge_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph,
-                                           (self.input_attention.mixer, self.input_attention.weight),
-                                           (self.forget_attention.mixer, self.forget_attention.weight), gi, gf, last_only=last_only)
+        gi, gf = self._small_time_gates(X, h0, train)
+        att_in = (self.input_attention.mixer, self.input_attention.weight)
+        att_f = (self.forget_attention.mixer, self.forget_attention.weight)
+        if train:
+            return ops.small_edge_cell_train(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, gi, gf)
+        return ops.small_edge_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, gi, gf, last_only=last_only)
 
     def _forward_small(self, X, h0, train=False):
         gi, gf = self._small_time_gates(X, h0, train)

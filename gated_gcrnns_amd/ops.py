@@ -2858,6 +2858,11 @@ def small_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, 
     recurrence in a second one with one workgroup per sequence. X: B x T x G x N, h0: B x F x N (user layout, fp32 / fp64) -> H: B x T x F x N,
     or B x 1 x F x N (the last state) with last_only. att_in / att_f: (mixer 1 x 1 x 2F, weight 1 x 1 x F x F) of the input / forget
     attention; gi / gf: time gates [T][B] or None."""
+    return _small_edge_forward(X, h0, wA, wB, bias, graph, att_in, att_f, gi, gf, last_only)
+
+
+def _small_edge_forward(X, h0, wA, wB, bias, graph, att_in, att_f, gi, gf, last_only):
+    """The two launches of gcrnn_small_edge_forward (inference entry point and the training function's forward)."""
     require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1])
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
@@ -2870,7 +2875,7 @@ def small_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, 
     if not small_edge_supported(N, csr.nnz, nnzs, G, F, Kin, Kst, dt, graph.E):
         raise GcrnnError('small_edge_cell_forward: shape outside the one-launch edge-gated kernel (small_edge_supported)')
     H = torch.empty((B, 1 if last_only else T, F, N), dtype=dt, device=X.device)
-    Ya = torch.empty((B, T, F, N), dtype=dt, device=X.device)
+    Ya = torch.empty((B, T, F, N), dtype=dt, device=X.device)         # the first launch's output, the second one's input; not kept
     bvec = bias.detach().contiguous().view(-1) if bias is not None else None
     if gi is not None:
         assert tuple(gi.shape) == (T, B) and tuple(gf.shape) == (T, B)
@@ -2885,6 +2890,98 @@ def small_edge_cell_forward(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, 
                                        _p(plan['t_rowptr']), _p(plan['t_edge']), _p(tvals), _p(Ya), _p(H),
                                        B, T, N, G, F, Kin, Kst, csr.nnz, nnzs, int(bool(last_only)), _stream()), 'small_edge_forward')
     return H
+
+
+def small_edge_training_supported(N, nnz, nnz_support, G, F, Kin, Kst, dtype, E=1):
+    if E != 1 or dtype not in (torch.float32, torch.float64):
+        return False
+    return bool(lib.gcrnn_small_edge_backward_supported(dtype_code(dtype), int(N), int(nnz), int(nnz_support), int(G), int(F),
+                                                        int(Kin), int(Kst)))
+
+
+def _edge_unfold(pwf, pbf, w, bias, mixer, weight):
+    """Gradients of one branch's taps w [F][1][K][C], bias, attention mixer and weight from the per-workgroup gradients of the folded
+    taps wf = [W w ; a1^T W w ; a2^T W w] (pwf [slots][F+2][K][C]) and of the folded bias (pbf [slots][F+2])."""
+    F = w.shape[0]
+    dwf, dbf = pwf.sum(dim=0).view(F + 2, -1), pbf.sum(dim=0)
+    w2, W, a = w.reshape(F, -1), weight.view(F, F), mixer.view(2, F)
+    top = dwf[:F] + a.t() @ dwf[F:]                                  # d loss / d (W w)
+    topb = dbf[:F] + a.t() @ dbf[F:]                                 # d loss / d (W b)
+    da = dwf[F:] @ (W @ w2).t()
+    dW = top @ w2.t()
+    db = None
+    if bias is not None:
+        bv = bias.view(F)
+        da = da + dbf[F:].unsqueeze(1) * (W @ bv).unsqueeze(0)
+        dW = dW + topb.unsqueeze(1) * bv.unsqueeze(0)
+        db = (W.t() @ topb).view(F, 1)
+    return (W.t() @ top).view(w.shape), db, da.reshape(mixer.shape), dW.view(weight.shape)
+
+
+class _SmallEdgeCell(torch.autograd.Function):
+    """Edge-gated small-graph cell with BPTT: forward = the two launches of the inference path (all states kept), backward = two launches
+    (small_edge_bptt_kernel, recurrence then input branch) plus the unfolding of the folded taps' gradients. Gradients for h0, the taps, the
+    bias, both attentions' mixer and weight and the time gates; none for X."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf, graph):
+        X, h0 = X.contiguous(), h0.contiguous()
+        H = _small_edge_forward(X, h0, wA, wB, bias, graph, (m_in, w_in), (m_f, w_f), gi, gf, False)
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf)
+        ctx.graph = graph
+        return H
+
+    @staticmethod
+    def backward(ctx, dH):
+        X, h0, H, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf = ctx.saved_tensors
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        dt, dev = X.dtype, X.device
+        graph = ctx.graph
+        fwd, adj, plan = graph.fwd[0], graph.adj[0], graph.edge_plan()
+        nnzs = plan['nnz']
+        R = F + 2
+        dPre = torch.empty((B, T, F, N), dtype=dt, device=dev)
+        pwfA = torch.empty((B * T, R, Kin, G), dtype=dt, device=dev)
+        pbfA = torch.empty((B * T, R), dtype=dt, device=dev)
+        pwfB = torch.empty((B, R, Kst, F), dtype=dt, device=dev)
+        pbfB = torch.empty((B, R), dtype=dt, device=dev)
+        dgi = dgf = None
+        if gi is not None:
+            gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
+            dgi = torch.empty((T, B), dtype=dt, device=dev)
+            dgf = torch.empty((T, B), dtype=dt, device=dev)
+        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+        bvec = bias.contiguous().view(-1) if bias is not None else None
+        # every operand is a named local (see _SmallCell.backward)
+        dHc, wAc, wBc = dH.contiguous(), wA.contiguous(), wB.contiguous()
+        wi, ai, wfo, afo = w_in.contiguous(), m_in.contiguous(), w_f.contiguous(), m_f.contiguous()
+        fval, aval, tvals = fwd.val(dt), adj.val(dt), _edge_support_values(graph, dt)
+        check(lib.gcrnn_small_edge_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
+                                            _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
+                                            _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
+                                            _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']),
+                                            _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB),
+                                            _p(dgi), _p(dgf), _p(dh0), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs, _stream()),
+              'small_edge_backward')
+        dwA, dbA, dm_in, dw_in = _edge_unfold(pwfA, pbfA, wAc, bias, ai, wi)
+        dwB, dbB, dm_f, dw_f = _edge_unfold(pwfB, pbfB, wBc, bias, afo, wfo)
+        db = dbA + dbB if bias is not None else None              # one bias, both branches
+        return None, dh0, dwA, dwB, db, dm_in, dw_in, dm_f, dw_f, dgi, dgf, None
+
+
+def small_edge_cell_train(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, gf=None):
+    """Training forward of the edge-gated small-graph cell (small_edge_training_supported shapes). att_in / att_f: (mixer, weight) of the
+    input / forget attention; gi / gf: differentiable time gates [T][B] or None. Gradients for everything but X: an X that wants one is
+    an error here (the module keeps the composed path for it), not a silent None."""
+    require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1])
+    if X.requires_grad and torch.is_grad_enabled():
+        raise GcrnnError('small_edge_cell_train: no gradient for X on this path (detach X, or use the composed path)')
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    if not small_edge_training_supported(N, graph.fwd[0].nnz, graph.edge_plan()['nnz'], G, F, Kin, Kst, X.dtype, graph.E):
+        raise GcrnnError('small_edge_cell_train: shape outside the edge-gated BPTT kernel (small_edge_training_supported)')
+    return _SmallEdgeCell.apply(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, graph)
 
 
 # ------------------------------------------------------------------------------------------ per-node head
