@@ -887,8 +887,10 @@ class GGCRNNCell(nn.Module):
 
     def forward_with_head(self, X, h0, weight, bias):
         """Inference of cell + output head Linear(F -> 1) shared by all nodes (the regression model's `multipMlp` head with one
-        output, reference architectures.py:1616-1627) with the head fused onto the h_t store of the fused step kernel: returns
-        y: B x T x 1 x N (fp32) without ever writing H in the user layout; None when this cell / input does not run on that path."""
+        output, reference architectures.py:1616-1627) with the head fused into a recurrence kernel's epilogue: the wide sequence-resident
+        kernel `fused_seq32_kernel` (head variant, ONE launch per forward: ops.fused_wide_head_supported) where it takes the problem, else the
+        per-step `fused_step_kernel` (EPI == 6, the head on its h_t store). Returns y: B x T x 1 x N (fp32) without ever writing H in the user
+        layout; None when this cell / input does not run on that path."""
         if torch.is_grad_enabled() or not self._use_fused(X, h0) or self.N % 8 != 0 or os.environ.get('GCRNN_NO_FUSED_HEAD'):      # env: A/B switch
             return None
         return self._forward_fused(X, h0, head=(weight, bias))

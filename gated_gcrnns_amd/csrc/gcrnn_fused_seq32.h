@@ -142,6 +142,9 @@ struct Seq32Args {
   const float* r1a; const float* r1b;                  // R1 (rank-1-weighted graph S[m][n] = a[m] b[n], plan of its 0/1 pattern): the factors [NP] fp32, zero for padding rows
   int stagger;                                         // > 0: workgroup i starts ((i / 8) % 8) * stagger shader cycles late (de-synchronises the CUs' memory phases for the whole launch)
   uint16_t* scr;                                       // VAR bit 2: the state scratch [workgroups][HS-1][NP slots][32] bf16 (out0 is null: no state image)
+  // VAR bit 3 (output head Linear(F -> 1) shared by all nodes, evaluated on the packed state in the epilogue; no user-layout output):
+  const float* head_w; const float* head_b;            // [F] fp32, one fp32 on the device (or null)
+  float* y0;                                           // y [B][nsteps][N] fp32
 };
 
 // this lane's id, re-derived where it is needed (two VALU instructions; volatile: neither hoisted nor kept): anything derived from the
@@ -188,6 +191,12 @@ struct Seq32Map {
                         + PFS;      // (the last PFS bytes: where gcrnn_fused_seq32p.h's L2 prefetches land -- LDS-DMA needs a destination, nobody reads it)
     return need <= 160 * 1024 ? need : 0;
   }
+  // VAR bit 3: the head's table in front of the inline-pack tile -- F weights, the bias at [64], and (HS > 1) one partial sum per slot
+  static constexpr int HEAD_TAB = 512 + (HS > 1 ? NP * 4 : 0);
+  static size_t lds_bytes_head(int64_t entries, bool inline_pack, bool r1 = false) {
+    const size_t need = lds_bytes(entries, inline_pack, r1);
+    return (need && need + HEAD_TAB <= 160 * 1024) ? need + HEAD_TAB : 0;
+  }
 };
 
 // VAR: bit 0 = the launch lays out the input itself (inline pack), bit 1 = it writes the user-layout output. Compile-time so that every way
@@ -203,6 +212,11 @@ struct Seq32Map {
 // chunk 0's epilogue of step t+1 stores to the address again, and that store has retired behind the vmcnt(0) of every later hop before the
 // next reload is requested. The addresses are re-used every step, so the reload carries sc1: it is served by L2 (where the line comes from
 // anyway, a step after its store) whatever this CU's vector L1 still holds of the previous step's line.
+// Bit 3 (with bit 2, without bit 1; MODE 0, persistent form: inference of cell + output head Linear(F -> 1) shared by all nodes): no state
+// image and no user-layout output either. The state hand-over is bit 2's; the epilogue adds y_t[n] = b + sum_f w[f] bf16(h_t[n][f]) on the
+// packed registers it holds anyway -- eight FMAs per lane and tile in feature order, the four quads of a node by two xor-shuffles (16, 32),
+// the chunks in ascending order through one LDS word per slot that the same lane writes and reads (a lane keeps its slots in every chunk:
+// slot = (wave * STILES + tile) * 16 + r) -- and the q == 0 lanes store the 4-byte results straight to y [B][T][N] (rows >= N never).
 // MODE 0: the recurrence (GATED: with the scalar time gates gi_t, gf_t known before step 0 -- they read (x_t, h0), never h_{t-1}).
 // MODE 1: the time gates' pre-pass for BOTH gates at once: an item (t, b) is one "sequence" of one step whose cell has 2 F outputs -- chunks
 //         0 .. F/32-1 the input gate's sub-cell, the rest the forget gate's (weights and biases concatenated by the caller) -- so the operand
@@ -224,7 +238,9 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   constexpr bool SONLY = (MODE == 2 || MODE == 4);      // state-only operand that is this launch's own output (XS = 0)
   constexpr bool PKV = (VAR & 1) != 0, USERV = (VAR & 2) != 0 && (MODE == 0 || MODE == 4);
   constexpr bool SCRV = (VAR & 4) != 0;      // state scratch in slot order, no state image
-  static_assert(!SCRV || (MODE == 0 && !SPLIT && (VAR & 2) != 0), "state scratch: the persistent forward with the user-layout output");
+  constexpr bool HEADV = (VAR & 8) != 0;     // output head in the epilogue, y instead of H
+  static_assert(!SCRV || (MODE == 0 && !SPLIT && ((VAR & 2) != 0 || HEADV)), "state scratch: the persistent forward with the user-layout output");
+  static_assert(!HEADV || (SCRV && (VAR & 2) == 0), "output head: on the state scratch, no user-layout output");
   constexpr int SCR_CH = NP * 64;            // bytes of one chunk's scratch rows [NP slots][32] bf16
   static_assert(MODE == 0 || ((MODE >= 1 && MODE <= 4) && !GATED), "modes");
   static_assert(MODE < 3 || (!R1 && !SPLIT), "modes 3, 4: uniform-weight graphs, persistent form");
@@ -320,6 +336,11 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   if (tid < GCRNN_HOP_COLUMN_PAD / 4) reinterpret_cast<uint32_t*>(smem + COL_OFF + entries * 32)[tid] = 0u;
   float* lbias = reinterpret_cast<float*>(smem + M::BIAS_OFF);
   if (tid < NCH * 32) lbias[tid] = a.bias ? a.bias[tid] : 0.f;
+  if constexpr (HEADV) {
+    float* ht = reinterpret_cast<float*>(smem + COL_OFF + entries * 32 + GCRNN_HOP_COLUMN_PAD + NP * 4 + (R1 ? 2 * NP * 4 : 0));
+    if (tid < F) ht[tid] = a.head_w[tid];
+    if (tid == F) ht[64] = a.head_b ? a.head_b[0] : 0.f;
+  }
   __syncthreads();
 
   if (a.stagger > 0) {
@@ -333,7 +354,8 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   const uint32_t lds0 = (uint32_t)reinterpret_cast<uintptr_t>(smem);
   if (lds0 != 0) __builtin_trap();        // the asm stream forms gather addresses from column words: the image must sit at LDS address 0
   const uint32_t lds_col = lds0 + COL_OFF;
-  char* xtile = wtab + NP * 4 + (R1 ? 2 * NP * 4 : 0);
+  [[maybe_unused]] float* htab = reinterpret_cast<float*>(wtab + NP * 4 + (R1 ? 2 * NP * 4 : 0));      // HEADV: w [F] | b at [64] | partial sums [NP slots] from [128]
+  char* xtile = wtab + NP * 4 + (R1 ? 2 * NP * 4 : 0) + (HEADV ? M::HEAD_TAB : 0);
 
   // wave-uniform, as a scalar integer (a lane mask would also be parked in a vector register)
   const int skip_hi = __builtin_amdgcn_readfirstlane((MODE == 3 || (MODE == 1 && a.flags && a.flags[0] != 0)) ? 1 : 0);      // (MODE 3: the operand is [0 | x_t])
@@ -981,6 +1003,32 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           p[3] = pack2bf(fast_tanh(a1[2] + bs[1][2]), fast_tanh(a1[3] + bs[1][3]));
         }
         pkd[i] = p;
+        if constexpr (HEADV) {
+          // the head on the bf16-ROUNDED state (the step kernel's definition): this lane's eight features in order, the node's four quads by
+          // two xor-shuffles (every lane of a column ends with the same bits), the chunks in ascending order through the slot's LDS word
+          // (weights, descriptor and bias are made where they are used: nothing of the head is held across the tiles, let alone the hops)
+          const float4* hwp = reinterpret_cast<const float4*>(htab + chunk * 32 + q * 8);
+          const float4 hw0 = hwp[0], hw1 = hwp[1];
+          float ys = __builtin_bit_cast(float, p[0] << 16) * hw0.x;
+          ys = __builtin_fmaf(hw0.y, __builtin_bit_cast(float, p[0] & 0xffff0000u), ys);
+          ys = __builtin_fmaf(hw0.z, __builtin_bit_cast(float, p[1] << 16), ys);
+          ys = __builtin_fmaf(hw0.w, __builtin_bit_cast(float, p[1] & 0xffff0000u), ys);
+          ys = __builtin_fmaf(hw1.x, __builtin_bit_cast(float, p[2] << 16), ys);
+          ys = __builtin_fmaf(hw1.y, __builtin_bit_cast(float, p[2] & 0xffff0000u), ys);
+          ys = __builtin_fmaf(hw1.z, __builtin_bit_cast(float, p[3] << 16), ys);
+          ys = __builtin_fmaf(hw1.w, __builtin_bit_cast(float, p[3] & 0xffff0000u), ys);
+          ys += __shfl_xor(ys, 16, 64);
+          ys += __shfl_xor(ys, 32, 64);
+          if (q == 0) {
+            float* yp = htab + 128 + (wave * STILES + i) * 16 + lane;      // (q == 0: lane = r)
+            if (HS > 1 && chunk > 0) ys = *yp + ys;
+            if (HS > 1 && !last) *yp = ys;
+            if (last && node < N) {
+              const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(a.y0 + ((int64_t)b * a.nsteps + step) * N, 0, N * 4, 0x00020000);
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, ys + htab[64]), rsrc_y, node * 4, 0, 0);
+            }
+          }
+        }
         if constexpr (SCRV) {
           // chunks 0 .. HS-2 into the workgroup's scratch at the lane's SLOT (padding slots store their zeros every step: the next step reads
           // them back); the last chunk's features stay in registers and leave through the user-layout tile only

@@ -340,6 +340,66 @@ extern "C" int gcrnn_fused_forward_wide_scratch_bf16(const void* xs, const void*
                            huser_last_only, Xuser_inline, rank1_a, rank1_b, stream);
 }
 
+// Inference of cell + output head Linear(F -> 1) shared by all nodes as ONE launch (gcrnn_fused_seq32.h VAR bit 3, instantiated in
+// gcrnn_fused_seq32h.hip): gcrnn_fused_forward_wide_scratch_bf16's arguments with Huser / huser_last_only replaced by head_w [F] fp32, head_b
+// (a DEVICE pointer to one fp32, or NULL; never read on the host) and Y [B][T][N] fp32: y_t[n] = head_b + sum_f head_w[f] bf16(h_t[n][f]),
+// the definition of the step kernel's fused head. No state image, no user-layout H; `scratch` as in the scratch form
+// (gcrnn_fused_forward_wide_scratch_bytes). gcrnn_fused_forward_wide_head_supported: 1 when the scratch form and the wide forward both take
+// the problem and the head's LDS table fits -- 0 for a split batch, GCRNN_SEQ32P=1, GCRNN_SEQ32_STATE_SCRATCH=0, weighted graphs.
+size_t gcrnn_seq32h_lds(int64_t F, int64_t G, int64_t K, int64_t entries, bool inline_pack, bool r1);
+int gcrnn_seq32h_forward(const Seq32Args& sa, int K, int HS, int XS, bool inline_pack, hipStream_t st);
+
+extern "C" int gcrnn_fused_forward_wide_head_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries,
+                                                       double uniform_w, int img16, int inline_pack) {
+  if (!gcrnn_fused_forward_wide_supported(B, T, N, F, G, K, entries, uniform_w, img16, inline_pack)) return 0;
+  if (B * T * N > 2147483647LL) return 0;
+  if (!seq32_wanted(B)) return 0;      // (a split batch: one launch per step)
+  if (gcrnn_fused_forward_wide_scratch_bytes(B, F, (img16 & 2) ? 1 : 0) < 0) return 0;
+  return gcrnn_seq32h_lds(F, G, K, entries, inline_pack != 0 && T > 2, (img16 & 2) != 0) ? 1 : 0;
+}
+
+extern "C" int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack, const float* bias,
+                                                  const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4,
+                                                  int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K,
+                                                  const float* head_w, const float* head_b, float* Y, const void* Xuser_inline,
+                                                  const float* rank1_a, const float* rank1_b, void* stream) {
+  if (!xs || !h0 || !wpack || !tile_nodes || !tile_off || !ell_col4 || !Y || !head_w) return GCRNN_ERR_NULL_POINTER;
+  if ((rank1_a == nullptr) != (rank1_b == nullptr)) return GCRNN_ERR_BAD_SHAPE;
+  if ((gi == nullptr) != (gf == nullptr) || (gi && Xuser_inline)) return GCRNN_ERR_BAD_SHAPE;
+  if (B <= 0 || T <= 0 || N <= 0 || N > NP || B > (1 << 24) || entries <= 0 || entries % 4) return GCRNN_ERR_BAD_SHAPE;
+  if (B * (NP * (F > G ? F : G) * 2) > 2147483647LL || B * T * N > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;   // 32-bit offsets
+  if (reinterpret_cast<uintptr_t>(Y) & 3) return GCRNN_ERR_BAD_SHAPE;
+  if (Xuser_inline && (N % 8 != 0 || (reinterpret_cast<uintptr_t>(Xuser_inline) & 15) || T * G * N > 2147483647LL)) return GCRNN_ERR_BAD_SHAPE;
+  if (F % 32 || F < 32 || G % 32 || G < 32) return GCRNN_ERR_UNSUPPORTED;
+  {      // (checked before anything is launched)
+    const int64_t need = seq32_scratch_need(B, F);
+    if (scratch_bytes < need || (need > 0 && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15)))) return GCRNN_ERR_BAD_SHAPE;
+  }
+  if (!rank1_a && !seq32_wanted(B) && seq32_split_wanted(B, F)) return GCRNN_ERR_UNSUPPORTED;      // a split batch hands h_t over between launches
+  Seq32Args sa{};
+  sa.x0 = (const uint16_t*)xs; sa.xstride = B * NP * G;
+  sa.hfirst = (const uint16_t*)h0;
+  sa.scr = (uint16_t*)scratch;
+  sa.wpack = (const uint4*)wpack; sa.bias = bias;
+  sa.head_w = head_w; sa.head_b = head_b; sa.y0 = Y;
+  sa.tile_nodes = tile_nodes; sa.tile_off = tile_off; sa.ell_col4 = (const uint2*)ell_col4;
+  sa.entries = (int)entries; sa.B = (int)B; sa.N = (int)N;
+  sa.nsteps = (int)T;
+  sa.gi0 = gi; sa.gf0 = gf; sa.gstride = B;
+  sa.r1a = rank1_a; sa.r1b = rank1_b;
+  {
+    const char* sg = getenv("GCRNN_SEQ32_STAGGER");
+    sa.stagger = sg ? atoi(sg) : 0;
+  }
+  const bool inline_pack = Xuser_inline != nullptr && T > 2;
+  if (inline_pack) {      // (the kernel lays out steps 2 .. T-1: gcrnn_fused_seq32.h)
+    sa.pk_src0 = (const uint16_t*)Xuser_inline; sa.pksrc_stride = G * N;
+    sa.pk_dst0 = const_cast<uint16_t*>(sa.x0); sa.pkdst_stride = sa.xstride;
+    sa.pk_stride = (int)(T * G * N);
+  }
+  return gcrnn_seq32h_forward(sa, (int)K, (int)(F / 32), (int)(G / 32), inline_pack, as_stream(stream));
+}
+
 
 // The two time gates' pre-pass as ONE launch over all (t, b) items (reference Utils/graphML.py:2357-2374): item i's operand (x_t, h0 of its
 // sequence) is loaded -- and with x_user laid out -- once for BOTH gates, whose sub-cells run as one cell of 2 F outputs on the wide kernel

@@ -561,6 +561,55 @@ def _fused_forward_wide(plan16, xs, h0s, hs, wA, wB, b32, B, T, N, F, G, K, H, l
           'fused_forward_wide')
 
 
+def _wide_head_plan(graph, B, T, N, F, G, K, inline, gated=False):
+    """The bf16-image plan (uniform-weight or rank-1) when the wide kernel's head variant (gcrnn_fused_forward_wide_head_bf16: cell + output
+    head Linear(F -> 1) as ONE launch on the state scratch) takes this problem, else None."""
+    if gated and inline:
+        return None
+    plan16 = _forward_plan16(graph)
+    if plan16 is None:
+        plan16 = _forward_plan16(graph, rank1=True)
+    if plan16 is None or F % 32 or G % 32:
+        return None
+    ok = lib.gcrnn_fused_forward_wide_head_supported(int(B), int(T), int(N), int(F), int(G), int(K), int(plan16['entries']),
+                                                     float(plan16.get('uniform_w', 0.0)), (3 if plan16.get('rank1') else 1) | (4 if gated else 0),
+                                                     1 if inline else 0)
+    return plan16 if ok else None
+
+
+def fused_wide_head_supported(graph, B, T, N, F, G, K, gated=False):
+    """True when cell + output head Linear(F -> 1) runs as ONE launch of the wide sequence-resident kernel (fused_cell_forward_wide_head;
+    csrc/gcrnn_fused_seq32.h VAR bit 3) at this shape: what the wide forward on the state scratch takes -- uniform-weight and rank-1-weighted
+    graphs, batches that are not split, F and G (padded) multiples of 32. gated: the time-gated cell."""
+    return _wide_head_plan(graph, B, T, N, F, G, K, False, gated=gated) is not None
+
+
+def _fused_forward_wide_head(plan16, xs, h0s, wA, wB, b32, B, T, N, F, G, K, hw, hb, Xinline, st, gi=None, gf=None, out=None):
+    """ONE launch: the recurrence with the head in its epilogue. Returns y [B][T][N] fp32 (`out`, or a fresh tensor). The scratch is allocated
+    per call on the current stream, as fused_state_scratch's callers do."""
+    dev = xs.device
+    scr = fused_state_scratch(plan16, B, F, dev)
+    assert scr is not None
+    if out is None:
+        out = torch.empty((B, T, N), dtype=torch.float32, device=dev)
+    else:
+        assert out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == (B, T, N) and out.is_contiguous(), 'out: contiguous fp32 [B][T][N]'
+    wpw = _fused_pack_weights_wide(wA.detach(), wB.detach(), plan16['uniform_w'], st)
+    check(lib.gcrnn_fused_forward_wide_head_bf16(_p(xs), _p(h0s), _p(scr), int(scr.numel()), _p(wpw), _p(b32), _p(gi), _p(gf),
+                                                 *_wide_graph_args(plan16), B, T, N, F, G, K, _p(hw), _p(hb), _p(out),
+                                                 _p(Xinline) if Xinline is not None else None,
+                                                 _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
+          'fused_forward_wide_head')
+    return out
+
+
+def fused_cell_forward_wide_head(X, h0, wA, wB, bias, graph, head, gates=None, gate_values=None, out=None):
+    """Inference of cell + output head as ONE launch of the wide kernel (fused_cell_forward's arguments; head = (weight 1 x F, bias [1] or
+    None)): y B x T x 1 x N fp32, a view of the [B][T][N] array the kernel writes -- `out`, when given (contiguous fp32 [B][T][N]). Raises where
+    fused_wide_head_supported says no; GCRNN_NO_WIDE_HEAD does not apply here (it switches the DISPATCH of fused_cell_forward off)."""
+    return fused_cell_forward(X, h0, wA, wB, bias, graph, gates=gates, gate_values=gate_values, head=head, _head_out=out, _head_wide='require')
+
+
 def _forward_plan16(graph, rank1=False):
     """The bf16-image plan of the forward graph (GraphOperator.fused_plan_img16: uniform-weight graphs only) or, with rank1, the plan of a
     rank-1-weighted graph (normalised adjacency): the plan of its 0/1 pattern + the two factor tables. None where the graph has no such
@@ -886,7 +935,7 @@ def fused_time_gate_pair(xs, h0s, gate_in, gate_f, graph, N, store_states=False,
 
 
 def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=False, gate_values=None, packed=None,
-                       last_only=False, head=None, native_out=False):
+                       last_only=False, head=None, native_out=False, _head_out=None, _head_wide=None):
     """Whole GGCRNNCell forward (un-gated or time-gated) on the fused bf16 step kernel.
 
     X: B x T x G x N bf16, h0: B x F x N bf16 (user layout) -> H: B x T x F x N bf16.
@@ -898,8 +947,9 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     last_only: H is B x 1 x F x N, the last state alone (the classification models' read-out); the user-layout store of the
     other steps is skipped.
     head: None, or (weight 1 x F, bias [1] or None) of an output head Linear(F -> 1) shared by all nodes (the regression model's
-    `multipMlp` head with one output, architectures.py:1616-1627): it is evaluated in the step kernel's epilogue, H is never written
-    in the user layout, and the function returns y: B x T x 1 x N (fp32) instead of H.
+    `multipMlp` head with one output, architectures.py:1616-1627): it is evaluated in the epilogue of the wide sequence-resident kernel
+    (ONE launch, fused_wide_head_supported; GCRNN_NO_WIDE_HEAD=1 switches that dispatch off) or else of the step kernel, H is never
+    written in the user layout, and the function returns y: B x T x 1 x N (fp32) instead of H.
     native_out: H is returned as a VIEW of the sequence-major state image the recurrence keeps anyway (hs [T][B][NPad][F]:
     hs.permute(1, 0, 3, 2)[..., :N] has the reference's B x T x F x N shape, reference graphML.py:2425-2427) -- the launches skip the
     user-layout copy of every h_t (a third of the bytes they write); callers that need contiguity call .contiguous() themselves.
@@ -929,12 +979,14 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     inline = False
     # inference through the user-layout H: the wide kernel then runs without a state image (fused_state_scratch) and hs is not allocated
     # here; a path that does need it allocates it below
-    lean = packed is None and head is None and not return_states and not native_out and N % 8 == 0
+    head_wide = head is not None and (_head_wide == 'require' or not os.environ.get('GCRNN_NO_WIDE_HEAD'))      # (the wide kernel's head variant may run)
+    lean = packed is None and (head is None or head_wide) and not return_states and not native_out and N % 8 == 0
     if packed is not None:
         xs, hs_all = packed
     elif gates is None and gate_values is None and X.data_ptr() % 16 == 0 and (
             fused_inline_pack_ok(plan, N, F, G, K) or (head is None and not os.environ.get('GCRNN_NO_INLINE_PACK')
-                                                       and fused_wide_plan(graph, B, T, N, F, G, K, True, rank1=True) is not None)):
+                                                       and fused_wide_plan(graph, B, T, N, F, G, K, True, rank1=True) is not None)
+            or (head_wide and not os.environ.get('GCRNN_NO_INLINE_PACK') and _wide_head_plan(graph, B, T, N, F, G, K, True) is not None)):
         # un-gated cell on a uniform-weight graph: only x_0 is packed here, launch t lays out x_{t+1} itself (LDS-DMA into the room
         # the missing weight image leaves, read back transposed after the epilogue) -- no pack pass over X
         xs, hs_all = fused_pack_inputs(X, h0, graph, first_only=True, states=not lean)
@@ -973,6 +1025,16 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
         assert not return_states and not last_only
         hw = head[0].detach().float().reshape(-1).contiguous()
         assert hw.numel() == F
+        wide_h = _wide_head_plan(graph, B, T, N, F, G, K, inline, gated=(gi is not None)) if (head_wide and evs is None) else None
+        if wide_h is not None:
+            # ONE launch of the wide sequence-resident kernel: no state image, no per-step launches, y written as [B][T][N]
+            hb = head[1].detach().float().reshape(-1).contiguous() if head[1] is not None else None
+            y = _fused_forward_wide_head(wide_h, xs, h0s, wA, wB, b32, B, T, N, F, G, K, hw, hb, X if inline else None, st, gi=gi, gf=gf, out=_head_out)
+            return y.unsqueeze(2)                                        # B x T x 1 x N (a view)
+        if _head_wide == 'require':
+            raise RuntimeError('fused_cell_forward_wide_head: the wide head form does not take this problem (fused_wide_head_supported)')
+        if hs.shape[0] == 0:                             # (lean, and not the wide head form after all: the step kernels keep the state image)
+            hs = torch.empty((T,) + tuple(h0s.shape[1:]), dtype=torch.bfloat16, device=dev)
         part = torch.empty((T, B, F // 16, N), dtype=torch.float32, device=dev)
         wpack = _fused_pack_weights(wA, wB, st)
         _fused_forward_steps(graph, xs, h0s, hs, wpack, b32, B, T, N, F, G, K, None, False, X if inline else None, st, gi, gf, evs, hw, part)

@@ -469,6 +469,19 @@ int gcrnn_fused_forward_wide_scratch_bf16(const void* xs, const void* h0, void* 
                                           const int32_t* tile_off, const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N,
                                           int64_t F, int64_t G, int64_t K, void* Huser, int huser_last_only, const void* Xuser_inline,
                                           const float* rank1_a, const float* rank1_b, void* stream);
+/* Inference of cell + output head Linear(F -> 1) shared by all nodes (the regression model's `multipMlp` head with one output) as ONE launch of
+ * the wide kernel: gcrnn_fused_forward_wide_scratch_bf16's arguments with Huser / huser_last_only replaced by head_w [F] fp32, head_b (a DEVICE
+ * pointer to one fp32, or NULL; never read on the host) and Y [B][T][N] fp32 (out): y_t[n] = head_b + sum_f head_w[f] bf16(h_t[n][f]), sums in
+ * fp32 in a fixed order. Neither a state image nor the user-layout H is written; scratch: gcrnn_fused_forward_wide_scratch_bytes.
+ * gcrnn_fused_forward_wide_head_supported (the arguments of gcrnn_fused_forward_wide_supported): 1 when the scratch form and the wide forward both
+ * take the problem and the head's table fits in LDS; 0 for split batches, weighted graphs, GCRNN_SEQ32P=1, GCRNN_SEQ32_STATE_SCRATCH=0. */
+int gcrnn_fused_forward_wide_head_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries, double uniform_w,
+                                            int img16, int inline_pack);
+int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack,
+                                       const float* bias, const float* gi, const float* gf, const int32_t* tile_nodes,
+                                       const int32_t* tile_off, const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N,
+                                       int64_t F, int64_t G, int64_t K, const float* head_w, const float* head_b, float* Y,
+                                       const void* Xuser_inline, const float* rank1_a, const float* rank1_b, void* stream);
 int gcrnn_fused_gate_pair_wide_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries, double uniform_w,
                                          int img16, int with_pack);
 /* The BPTT data chain as ONE launch of the wide kernel: gcrnn_fused_backward_data_bf16's contract (seed included), with wpackT =
