@@ -206,9 +206,10 @@ class GraphOperator(object):
         usual normalisations -- D^-1/2 A D^-1/2 (a = b = d^-1/2; reference Utils/graphTools.py:64 normalizeAdjacency), the random-walk forms
         D^-1 A / A D^-1, any of them divided by an eigenvalue. Found by breadth-first propagation of a[m] = S[m][n] / b[n] over the bipartite
         graph of rows and columns (numpy over whole frontiers; depth = the graph's diameter, so rounding does not pile up along a path),
-        polished by two alternating averaging sweeps, and verified on EVERY non-zero to 8 eps of the precision the GSO was given in (fp32-
-        representable values: 9.5e-7; fp64: 1.8e-15) -- an almost-rank-1 operator is NOT replaced by a rank-1 approximation (the
-        fp32-accurate path's whole budget is 1e-5). adjoint: the factors of S^T (a and b swap)."""
+        polished by two alternating averaging sweeps (as corrections to the factors, so that a hub's long column adds no rounding of its
+        own), and verified on EVERY non-zero to 8 eps of the precision the GSO was given in (fp32-representable values: 9.5e-7; fp64:
+        1.8e-15) -- the polished factors, else the propagated ones; an almost-rank-1 operator is NOT replaced by a rank-1 approximation
+        (the fp32-accurate path's whole budget is 1e-5). adjoint: the factors of S^T (a and b swap)."""
         key = '_rank1_adj' if adjoint else '_rank1'
         if key in self.__dict__:
             return self.__dict__[key]
@@ -245,14 +246,26 @@ class GraphOperator(object):
                             m_u, first = np.unique(rows[e], return_index=True)
                             a[m_u] = val[e[first]] / b[col[e[first]]]
                             seen_a[m_u] = True; new_rows[m_u] = True
+                def exact(a, b):
+                    return bool(np.all(np.isfinite(a)) and np.all(np.isfinite(b)) and np.all(np.abs(a[rows] * b[col] - val) <= 8.0 * eps * np.abs(val)))
+
                 with np.errstate(divide='ignore', invalid='ignore'):
-                    for _ in range(2):                                            # polish: each factor = the mean of what its non-zeros say
-                        cnt_a = np.bincount(rows, minlength=N); cnt_b = np.bincount(col, minlength=N)
-                        a_new = np.bincount(rows, weights=val / b[col], minlength=N) / np.maximum(cnt_a, 1)
-                        a = np.where(cnt_a > 0, a_new, a)
-                        b_new = np.bincount(col, weights=val / a[rows], minlength=N) / np.maximum(cnt_b, 1)
-                        b = np.where(cnt_b > 0, b_new, b)
-                    good = np.all(np.isfinite(a)) and np.all(np.isfinite(b)) and np.all(np.abs(a[rows] * b[col] - val) <= 8.0 * eps * np.abs(val))
+                    # polish: each factor = the mean of what its non-zeros say, as a correction a (1 + mean(q / a - 1)): the terms of the mean
+                    # are of the size of the factors' rounding, so the sum over a long row or column (a hub: hundreds of quotients) adds no
+                    # rounding of its own -- a plain mean of the quotients loses about sqrt(count) eps and fails the 8 eps below at fp64
+                    cnt_a = np.bincount(rows, minlength=N); cnt_b = np.bincount(col, minlength=N)
+                    pa, pb = a, b
+                    for _ in range(2):
+                        da = np.bincount(rows, weights=val / pb[col] / pa[rows] - 1.0, minlength=N) / np.maximum(cnt_a, 1)
+                        pa = np.where(cnt_a > 0, pa * (1.0 + da), pa)
+                        db = np.bincount(col, weights=val / pa[rows] / pb[col] - 1.0, minlength=N) / np.maximum(cnt_b, 1)
+                        pb = np.where(cnt_b > 0, pb * (1.0 + db), pb)
+                    # whichever verifies on every non-zero: the polished factors, else the propagated ones as they are
+                    good = exact(pa, pb)
+                    if good:
+                        a, b = pa, pb
+                    else:
+                        good = exact(a, b)
                 if good:
                     # balance the two factors (any split works; this one keeps both in fp32's comfortable range)
                     na, nb_ = np.abs(a[seen_a]).max(), np.abs(b[seen_b]).max()

@@ -12,6 +12,8 @@ def bf16_round(a):
 
 
 def _uniform_cell(N, G, F, K, seed, time_gating=False):
+    """Cell on a uniform-weight graph. The SYMMETRIC support is deliberate here (forward and adjoint plan coincide, so the variants of one
+    launch can be compared bit for bit); the same kernels on directed graphs are pinned in tests/test_directed_uniform.py."""
     import gated_gcrnns_amd.Utils.graphML as gml
     rng = np.random.default_rng(seed)
     W = (rng.random((N, N)) < 10.0 / N).astype(np.float64)
