@@ -632,15 +632,21 @@ class GGCRNNCell(nn.Module):
         return self.weight_A.dtype == X.dtype and h0.dtype == X.dtype and self._small_takes(X)
 
     def _use_small_training(self, X, h0):
-        """Small graphs, gradients wanted for parameters / h0 but not for X: forward and BPTT are one launch each."""
-        if not torch.is_grad_enabled() or X.requires_grad:
+        """Small graphs, gradients wanted for parameters / h0, and for X where the BPTT kernels' dx variants take the shape
+        (ops.small_input_grad_supported: un-gated, time-gated and node-gated cells): forward and BPTT are one launch each."""
+        if not torch.is_grad_enabled():
             return False
         if not self._sigma_is_tanh():
             return False
         if self.spatial_gating is not None and not self._small_node_gating_ok(X, True):
             return False
-        return self.weight_A.dtype == X.dtype and h0.dtype == X.dtype and \
-            ops.small_training_supported(self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E)
+        if self.weight_A.dtype != X.dtype or h0.dtype != X.dtype:
+            return False
+        shape = (self.N, self.graph.fwd[0].nnz, self.G, self.F, self.Kin, self.Kst, X.dtype, self.E)
+        if X.requires_grad:
+            return ops.small_input_grad_supported(*shape, gated=self.time_gating == True or self.spatial_gating is not None,  # noqa: E712
+                                                  node_gates=self.spatial_gating is not None)
+        return ops.small_training_supported(*shape)
 
     def _small_time_gates(self, X, h0, train=False):
         """(gi, gf), each [T][B], of a time-gated cell on a small graph; (None, None) without time gating."""

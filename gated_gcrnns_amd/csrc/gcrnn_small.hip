@@ -174,9 +174,11 @@ extern "C" int gcrnn_small_forward(int dtype, const void* X, const void* h0, con
 //   carry_{t-1} = gf_t sum_k (B_k^T dpre_t) (S^T)^k   in Horner form with CSR(S)   (adjoint of graphML.py:118-135)
 // The shifted signals z_k are recomputed (K-1 hops) instead of stored. Per-sequence partial sums go to
 //   pA [B][2][F][Kin][G], pB [B][2][F][Kst][F], pb [B][F]  (the caller adds them up in a fixed order: deterministic).
-// dX is not produced.
+// DX = true also produces the input gradient: with z = [x | h] the adjoint runs as ONE Horner chain over all G + F channels,
+//   acc <- acc S^T + [gi A_k | gf B_k]^T dpre_t,  k = K-1 .. 0;   rows 0..G-1 of the result are dX_t, the rest is carry_{t-1}
+// (the two z buffers hold C rows each, so the chain needs no more LDS than the carry alone). DX = false: dX is not produced.
 // ------------------------------------------------------------------------------------------
-template <typename T, int K, bool GATED, int P>      // P = passes of 1024 threads over the 2 F C weight slots and the F N outputs
+template <typename T, int K, bool GATED, int P, bool DX>      // P = passes of 1024 threads over the 2 F C weight slots and the F N outputs
 __global__ __launch_bounds__(1024) void small_cell_bwd_kernel(
     const T* __restrict__ X,        // [B][Tn][G][N]
     const T* __restrict__ h0,       // [B][F][N]
@@ -188,6 +190,7 @@ __global__ __launch_bounds__(1024) void small_cell_bwd_kernel(
     const int32_t* __restrict__ arowptr, const int32_t* __restrict__ acol, const T* __restrict__ aval,       // CSR(S)
     T* __restrict__ pA, T* __restrict__ pB, T* __restrict__ pb, T* __restrict__ dgi, T* __restrict__ dgf,
     T* __restrict__ dh0,            // [B][F][N] or null
+    T* __restrict__ dX,             // [B][Tn][G][N] (DX)
     int Tn, int N, int G, int F, int Kin, int Kst, int nnz, int B) {
   extern __shared__ __attribute__((aligned(16))) char smem_small[];
   const int C = G + F;
@@ -337,6 +340,35 @@ __global__ __launch_bounds__(1024) void small_cell_bwd_kernel(
     // ---- carry_{t-1} = gf sum_k (B_k^T dpre)(S^T)^k : acc <- acc S^T + B_k^T dpre, k = Kst-1 .. 0 (acc in zA / zB, [F][Ns])
     T* ac = zA;
     T* an = zB;
+    if (DX) {
+      // one chain over all C channels: channel c < G takes the input taps (gate gi), c >= G the state taps (gate gf); a filter
+      // with fewer taps than K adds nothing at its missing levels, and its accumulator is still zero there
+      T* dxt = dX + ((size_t)b * Tn + t) * GN;
+      for (int k = K - 1; k >= 0; --k) {
+        for (int i = tid; i < CN; i += 1024) {
+          const int c = i / N, n = i - c * N;
+          T acc = T(0);
+          if (c < G) {
+            if (k < Kin) {
+              for (int f = 0; f < F; ++f) acc += wAl[(f * Kin + k) * G + c] * dpre[f * Ns + n];
+              acc *= gin;
+            }
+          } else if (k < Kst) {
+            for (int f = 0; f < F; ++f) acc += wBl[(f * Kst + k) * F + (c - G)] * dpre[f * Ns + n];
+            acc *= gfo;
+          }
+          if (k < K - 1) {
+            const T* ar = ac + c * Ns;
+            for (int j = arpl[n]; j < arpl[n + 1]; ++j) acc += avall[j] * ar[acoll[j]];
+          }
+          if (k > 0) an[c * Ns + n] = acc;
+          else if (c < G) dxt[i] = acc;
+          else carry[(c - G) * Ns + n] = acc;
+        }
+        __syncthreads();
+        T* tmp = ac; ac = an; an = tmp;
+      }
+    } else
     for (int k = Kst - 1; k >= 0; --k) {
       T* dst = (k == 0) ? carry : an;
       for (int i = tid; i < FN; i += 1024) {
@@ -392,40 +424,40 @@ extern "C" int gcrnn_small_backward_supported(int dtype, int64_t N, int64_t nnz,
   return small_bwd_lds_bytes(dtype, N, nnz, G, F, Kin, Kst) <= 150 * 1024 ? 1 : 0;
 }
 
-template <typename T, int K, bool GATED, int P>
+template <typename T, int K, bool GATED, int P, bool DX>
 static int small_bwd_launch(const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
                             const void* bias, const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col,
                             const void* val, const int32_t* arowptr, const int32_t* acol, const void* aval, void* pA, void* pB,
-                            void* pb, void* dgi, void* dgf, void* dh0, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
-                            int64_t Kin, int64_t Kst, int64_t nnz, size_t lds, hipStream_t st) {
-  auto kern = small_cell_bwd_kernel<T, K, GATED, P>;
+                            void* pb, void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G,
+                            int64_t F, int64_t Kin, int64_t Kst, int64_t nnz, size_t lds, hipStream_t st) {
+  auto kern = small_cell_bwd_kernel<T, K, GATED, P, DX>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
   kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)H, (const T*)dH, (const T*)wA, (const T*)wB,
                                       (const T*)bias, (const T*)gi, (const T*)gf, rowptr, col, (const T*)val, arowptr, acol,
-                                      (const T*)aval, (T*)pA, (T*)pB, (T*)pb, (T*)dgi, (T*)dgf, (T*)dh0, (int)Tn, (int)N,
-                                      (int)G, (int)F, (int)Kin, (int)Kst, (int)nnz, (int)B);
+                                      (const T*)aval, (T*)pA, (T*)pB, (T*)pb, (T*)dgi, (T*)dgf, (T*)dh0, (T*)dX, (int)Tn,
+                                      (int)N, (int)G, (int)F, (int)Kin, (int)Kst, (int)nnz, (int)B);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
 
-template <typename T>
+template <typename T, bool DX>
 static int small_bwd_dispatch(bool gated, int64_t K, const void* X, const void* h0, const void* H, const void* dH,
                               const void* wA, const void* wB, const void* bias, const void* gi, const void* gf,
                               const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* arowptr,
                               const int32_t* acol, const void* aval, void* pA, void* pB, void* pb, void* dgi, void* dgf,
-                              void* dh0, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
-                              int64_t nnz, size_t lds, hipStream_t st) {
+                              void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                              int64_t Kst, int64_t nnz, size_t lds, hipStream_t st) {
   const bool two = F * N <= 2048 && 2 * F * (G + F) <= 2048;      // the drivers' sizes: fewer accumulators per thread, no spills
 #define GCRNN_SMALL_BWD_ARGS X, h0, H, dH, wA, wB, bias, gi, gf, rowptr, col, val, arowptr, acol, aval, pA, pB, pb, dgi, dgf, \
-                             dh0, B, Tn, N, G, F, Kin, Kst, nnz, lds, st
+                             dh0, dX, B, Tn, N, G, F, Kin, Kst, nnz, lds, st
 #define GCRNN_SMALL_BWD_CASE(KK)                                                                                   \
   if (K == KK) {                                                                                                   \
-    if (gated) return two ? small_bwd_launch<T, KK, true, 2>(GCRNN_SMALL_BWD_ARGS)                                 \
-                          : small_bwd_launch<T, KK, true, 4>(GCRNN_SMALL_BWD_ARGS);                                \
-    return two ? small_bwd_launch<T, KK, false, 2>(GCRNN_SMALL_BWD_ARGS)                                           \
-               : small_bwd_launch<T, KK, false, 4>(GCRNN_SMALL_BWD_ARGS);                                          \
+    if (gated) return two ? small_bwd_launch<T, KK, true, 2, DX>(GCRNN_SMALL_BWD_ARGS)                             \
+                          : small_bwd_launch<T, KK, true, 4, DX>(GCRNN_SMALL_BWD_ARGS);                            \
+    return two ? small_bwd_launch<T, KK, false, 2, DX>(GCRNN_SMALL_BWD_ARGS)                                       \
+               : small_bwd_launch<T, KK, false, 4, DX>(GCRNN_SMALL_BWD_ARGS);                                      \
   }
   GCRNN_SMALL_BWD_CASE(1)
   GCRNN_SMALL_BWD_CASE(2)
@@ -437,23 +469,48 @@ static int small_bwd_dispatch(bool gated, int64_t K, const void* X, const void* 
   return GCRNN_ERR_UNSUPPORTED;
 }
 
+static int small_backward_entry(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                                const void* wB, const void* bias, const void* gi, const void* gf, const int32_t* rowptr,
+                                const int32_t* col, const void* val, const int32_t* arowptr, const int32_t* acol,
+                                const void* aval, void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0, void* dX,
+                                bool dx, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                int64_t nnz, void* stream) {
+  if (!X || !h0 || !H || !dH || !wA || !wB || !rowptr || !arowptr || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
+  if (dx && !dX) return GCRNN_ERR_NULL_POINTER;
+  if (nnz > 0 && (!col || !val || !acol || !aval)) return GCRNN_ERR_NULL_POINTER;
+  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
+  if (dx && dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (B <= 0 || T <= 0 || B > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
+  if (dx && (N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0 || nnz < 0)) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_backward_supported(dtype, N, nnz, G, F, Kin, Kst)) return GCRNN_ERR_UNSUPPORTED;
+  const size_t lds = small_bwd_lds_bytes(dtype, N, nnz, G, F, Kin, Kst);
+  const int64_t K = Kin > Kst ? Kin : Kst;
+#define GCRNN_SMALL_BWD_CALL(TT, DD)                                                                                          \
+  small_bwd_dispatch<TT, DD>(gi != nullptr, K, X, h0, H, dH, wA, wB, bias, gi, gf, rowptr, col, val, arowptr, acol, aval, pA, \
+                             pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, lds, as_stream(stream))
+  if (dtype == GCRNN_F32) return dx ? GCRNN_SMALL_BWD_CALL(float, true) : GCRNN_SMALL_BWD_CALL(float, false);
+  return dx ? GCRNN_SMALL_BWD_CALL(double, true) : GCRNN_SMALL_BWD_CALL(double, false);
+#undef GCRNN_SMALL_BWD_CALL
+}
+
 extern "C" int gcrnn_small_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
                                     const void* wB, const void* bias, const void* gi, const void* gf, const int32_t* rowptr,
                                     const int32_t* col, const void* val, const int32_t* arowptr, const int32_t* acol,
                                     const void* aval, void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0,
                                     int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
                                     int64_t nnz, void* stream) {
-  if (!X || !h0 || !H || !dH || !wA || !wB || !rowptr || !arowptr || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
-  if (nnz > 0 && (!col || !val || !acol || !aval)) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
-  if (B <= 0 || T <= 0 || B > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
-  if (!gcrnn_small_backward_supported(dtype, N, nnz, G, F, Kin, Kst)) return GCRNN_ERR_UNSUPPORTED;
-  const size_t lds = small_bwd_lds_bytes(dtype, N, nnz, G, F, Kin, Kst);
-  const int64_t K = Kin > Kst ? Kin : Kst;
-  if (dtype == GCRNN_F32)
-    return small_bwd_dispatch<float>(gi != nullptr, K, X, h0, H, dH, wA, wB, bias, gi, gf, rowptr, col, val, arowptr, acol,
-                                     aval, pA, pB, pb, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, nnz, lds, as_stream(stream));
-  return small_bwd_dispatch<double>(gi != nullptr, K, X, h0, H, dH, wA, wB, bias, gi, gf, rowptr, col, val, arowptr, acol,
-                                    aval, pA, pB, pb, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, nnz, lds, as_stream(stream));
+  return small_backward_entry(dtype, X, h0, H, dH, wA, wB, bias, gi, gf, rowptr, col, val, arowptr, acol, aval, pA, pB, pb, dgi,
+                              dgf, dh0, nullptr, false, B, T, N, G, F, Kin, Kst, nnz, stream);
+}
+
+// The same backward pass with the input gradient dX [B][T][G][N] as well (the DX variant of the kernel: same LDS image).
+extern "C" int gcrnn_small_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                                       const void* wB, const void* bias, const void* gi, const void* gf, const int32_t* rowptr,
+                                       const int32_t* col, const void* val, const int32_t* arowptr, const int32_t* acol,
+                                       const void* aval, void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0,
+                                       void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                       int64_t Kst, int64_t nnz, void* stream) {
+  return small_backward_entry(dtype, X, h0, H, dH, wA, wB, bias, gi, gf, rowptr, col, val, arowptr, acol, aval, pA, pB, pb, dgi,
+                              dgf, dh0, dX, true, B, T, N, G, F, Kin, Kst, nnz, stream);
 }

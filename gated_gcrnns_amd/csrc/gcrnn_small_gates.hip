@@ -220,7 +220,10 @@ __global__ __launch_bounds__(1024) void small_gate_fwd_kernel(
   }
 }
 
-template <typename T>
+// DX = true also writes this gate's share of the input gradient, pdX[b][g][t] = sum_k (A_k^T dpre_t)(S^T)^k [G x N] (Horner, on
+// the matrix cores): the hop levels Zx of x_t are free once dA has consumed them, so levels 0 / 1 serve as the chain's
+// ping-pong accumulators (Kin = 1 has no hop and needs none) -- no LDS beyond the plain backward's.
+template <typename T, bool DX>
 __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
     const T* __restrict__ X, const T* __restrict__ h0, const T* __restrict__ wA2, const T* __restrict__ wB2,
     const T* __restrict__ bias2, const T* __restrict__ lw2, const T* __restrict__ Sd,
@@ -231,6 +234,7 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
     T* __restrict__ plw,            // [B][2][F*N]
     T* __restrict__ plb,            // [B][2]
     T* __restrict__ pdh0,           // [B][2][F][N] or null
+    T* __restrict__ pdX,            // [B][2][Tn][G][N] (DX)
     int Tn, int N, int G, int F, int Kin, int Kst, int B) {
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_gate[];
@@ -292,6 +296,45 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
       dA = tile_mac<T>(dA, ap, 4, bp, 4, c.N4 >> 2);
     }
     __syncthreads();                 // Zx and dP are rewritten by the next step
+    if (DX) {
+      T* dxt = pdX + (((size_t)b * 2 + g) * Tn + t) * G * N;
+      const int tilesG = (G + 15) >> 4;
+      T* ac = c.Zx;
+      T* an = c.Zx + (size_t)c.G4 * Ns;               // level 1: exists whenever a hop is needed (Kin >= 2)
+      for (int k = Kin - 1; k >= 0; --k) {
+        for (int tile = c.wave; tile < tilesG * c.tilesN; tile += 16) {
+          const int i0 = (tile / c.tilesN) << 4, j0 = (tile % c.tilesN) << 4;
+          acc_t acc = {0, 0, 0, 0};
+          const int gg = i0 + c.li;
+          const bool arow = gg < G;
+          // A = A_k^T (i = g, k = f) = WA[f][k G4 + g] (rows f >= F are zero), B = dpre (k = f, j = n; rows f >= F are zero)
+          const T* wp = c.WA + (size_t)k * c.G4 + (arow ? gg : 0);
+          for (int s0 = 0; s0 < c.F4; s0 += 4) {
+            const int f = s0 + c.lk;
+            const T a = arow ? wp[(size_t)f * c.KGs] : T(0);
+            acc = Mf<T>::mma(a, dP[f * Ns + j0 + c.li], acc);
+          }
+          if (k < Kin - 1) {
+            // A = acc (i = g, k = m), B = S^T (k = m, j = n) = S[n][m]
+            const int nr = j0 + c.li;
+            const T* ap = arow ? ac + gg * Ns + c.lk : c.zrow + c.lk;
+            const T* bp = (nr < N) ? c.S + (size_t)nr * Ns + c.lk : c.zrow + c.lk;
+            acc = tile_mac<T>(acc, ap, 4, bp, 4, c.N4 >> 2);
+          }
+          const int n = j0 + c.li;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int gr = i0 + Mf<T>::row(c.lane, r);
+            if (gr < G && n < N) {
+              if (k > 0) an[gr * Ns + n] = acc[r];
+              else dxt[(size_t)gr * N + n] = acc[r];
+            }
+          }
+        }
+        __syncthreads();
+        T* tmp = ac; ac = an; an = tmp;
+      }
+    }
   }
   // ---- per-sequence results
   if (c.tid == 0) plb[(size_t)b * 2 + g] = dlb;
@@ -451,18 +494,20 @@ extern "C" int gcrnn_small_gates_forward(int dtype, const void* X, const void* h
   return gates_fwd_launch<double>(X, h0, wA2, wB2, bias2, lw2, lb2, Sdense, gate, B, T, N, G, F, Kin, Kst, as_stream(stream));
 }
 
-template <typename T>
+template <typename T, bool DX>
 static int gates_bwd_launch(const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2, const void* lw2,
                             const void* Sd, const void* dsum, void* pA, void* pB, void* pb, void* plw, void* plb, void* pdh0,
-                            int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, hipStream_t st) {
+                            void* pdX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                            hipStream_t st) {
   const size_t lds = gate_lds<T>(N, G, F, Kin, true);
-  auto kern = small_gate_bwd_kernel<T>;
+  auto kern = small_gate_bwd_kernel<T, DX>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
   kern<<<dim3((unsigned)B, 2), 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)wA2, (const T*)wB2, (const T*)bias2,
                                                 (const T*)lw2, (const T*)Sd, (const T*)dsum, (T*)pA, (T*)pB, (T*)pb, (T*)plw,
-                                                (T*)plb, (T*)pdh0, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst, (int)B);
+                                                (T*)plb, (T*)pdh0, (T*)pdX, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
+                                                (int)B);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -475,8 +520,26 @@ extern "C" int gcrnn_small_gates_backward(int dtype, const void* X, const void* 
   if (B <= 0 || T <= 0 || B > 65535 * 32768LL) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_gates_supported(dtype, N, G, F, Kin, Kst, 1)) return GCRNN_ERR_UNSUPPORTED;
   if (dtype == GCRNN_F32)
-    return gates_bwd_launch<float>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, B, T, N, G, F, Kin, Kst,
-                                   as_stream(stream));
-  return gates_bwd_launch<double>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, B, T, N, G, F, Kin, Kst,
-                                  as_stream(stream));
+    return gates_bwd_launch<float, false>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, nullptr, B, T, N, G,
+                                          F, Kin, Kst, as_stream(stream));
+  return gates_bwd_launch<double, false>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, nullptr, B, T, N, G,
+                                         F, Kin, Kst, as_stream(stream));
+}
+
+// The same backward pass with each gate's share of the input gradient, pdX [B][2][T][G][N] (the caller adds the two gates in a
+// fixed order, as for pdh0). Same LDS image as the plain backward: gcrnn_small_gates_supported(..., backward = 1) answers for both.
+extern "C" int gcrnn_small_gates_backward_dx(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2,
+                                             const void* bias2, const void* lw2, const void* Sdense, const void* dsum, void* pA,
+                                             void* pB, void* pb, void* plw, void* plb, void* pdh0, void* pdX, int64_t B,
+                                             int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, void* stream) {
+  if (!X || !h0 || !wA2 || !wB2 || !lw2 || !Sdense || !dsum || !pA || !pB || !pb || !plw || !plb || !pdX)
+    return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (B <= 0 || T <= 0 || B > 65535 * 32768LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_gates_supported(dtype, N, G, F, Kin, Kst, 1)) return GCRNN_ERR_UNSUPPORTED;
+  if (dtype == GCRNN_F32)
+    return gates_bwd_launch<float, true>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, pdX, B, T, N, G, F,
+                                         Kin, Kst, as_stream(stream));
+  return gates_bwd_launch<double, true>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, pdX, B, T, N, G, F,
+                                        Kin, Kst, as_stream(stream));
 }

@@ -176,8 +176,13 @@ size_t dense_fwd_lds(int64_t N, int64_t G, int64_t F, int64_t K) {
 
 // ------------------------------------------------------------------------------------------------------------------
 // backward (BPTT); same contract as small_cell_bwd_kernel in gcrnn_small.hip
+// DX = true also produces dX: the adjoint is one Horner chain over all C = G + F channels,
+//   acc [C x N] <- acc S^T + g . (W_k^T dpre),   W_k = [A_k | B_k] [F x C],   g[c][n] = gi[n] (c < G) or gf[n] (c >= G),
+// whose rows 0..G-1 are dX_t and whose other rows are carry_{t-1}. The gates depend on the OUTPUT element (row kind, node), so
+// they scale the tap product after the MFMA chain; per-node gates (node-gated cells) cost nothing extra. The state taps' image
+// WBt [Kst][F4][Fs] is replaced by the combined WT [K][F4][Cs1], the only difference in the LDS need.
 // ------------------------------------------------------------------------------------------------------------------
-template <typename T, bool GATED, int MAXW>
+template <typename T, bool GATED, int MAXW, bool DX>
 __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     const T* __restrict__ X, const T* __restrict__ h0, const T* __restrict__ H, const T* __restrict__ dH,
     const T* __restrict__ wA, const T* __restrict__ wB, const T* __restrict__ bias,
@@ -188,6 +193,7 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     T* __restrict__ pb,             // [B][F]
     T* __restrict__ dgi, T* __restrict__ dgf,                 // [B][Tn][N] gradients of the gates (GATED)
     T* __restrict__ dh0,
+    T* __restrict__ dX,             // [B][Tn][G][N] (DX)
     int Tn, int N, int G, int F, int Kin, int Kst, int B,
     int64_t gsb, int64_t gst, int64_t gsn) {     // gate element (b, t, n) sits at b gsb + t gst + n gsn (dgi / dgf are dense)
   typedef typename Mf<T>::acc acc_t;
@@ -204,7 +210,8 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
   T* dpre = Z1 + (size_t)C4 * Ns;                  // [F4][Ns]  (rows >= F stay zero: k-padding of the B operands)
   T* carry = dpre + (size_t)F4 * Ns;               // [F4][Ns]
   T* WBt = carry + (size_t)F4 * Ns;                // [Kst][F4 (f)][Fs (f2)]   w_B[f][k][f2]
-  T* WAl = WBt + (size_t)Kst * F4 * Fs;            // GATED: [F][K][Cs] combined taps
+  const int Cs1 = lds_stride<T>(C + 1);            // DX: WBt holds [K][F4 (f)][Cs1 (c)] = [w_A | w_B][f][k][c], column C zero
+  T* WAl = WBt + (DX ? (size_t)K * F4 * Cs1 : (size_t)Kst * F4 * Fs);      // GATED: [F][K][Cs] combined taps
   T* red = WAl + (GATED ? (size_t)F * K * Cs : 0);     // [64]
   T* zrow = red + 64;                                  // [max(Ns, K Cs)] zeros: what masked lanes read
   const int ZR = Ns > K * Cs ? Ns : K * Cs;
@@ -221,6 +228,18 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
   }
   for (int i = tid; i < 2 * C4 * Ns + 2 * F4 * Ns; i += 1024) Z0[i] = T(0);        // Z0, Z1, dpre, carry are contiguous
   for (int i = tid; i < ZR + (GATED ? 2 * Ns + 2 * tilesF * Ns : 0); i += 1024) zrow[i] = T(0);
+  if (DX) {
+    for (int i = tid; i < K * F4 * Cs1; i += 1024) {
+      const int k = i / (F4 * Cs1), rem = i - k * (F4 * Cs1);
+      const int f = rem / Cs1, c = rem - f * Cs1;
+      T v = T(0);
+      if (f < F && c < C) {
+        if (c < G) { if (k < Kin) v = wA[((size_t)f * Kin + k) * G + c]; }
+        else       { if (k < Kst) v = wB[((size_t)f * Kst + k) * F + (c - G)]; }
+      }
+      WBt[i] = v;
+    }
+  } else
   for (int i = tid; i < Kst * F4 * Fs; i += 1024) {
     const int k = i / (F4 * Fs), rem = i - k * (F4 * Fs);
     const int f = rem / Fs, f2 = rem - f * Fs;
@@ -372,6 +391,41 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     // ---- carry_{t-1}: acc <- gf B_k^T dpre + acc S^T, k = Kst-1 .. 0
     T* ac = Z0;
     T* an = Z1;
+    if (DX) {
+      T* dxt = dX + ((size_t)b * Tn + t) * GN;
+      for (int k = K - 1; k >= 0; --k) {
+        const T* wk = WBt + (size_t)k * F4 * Cs1;
+        for (int tile = wave; tile < tilesC * tilesN; tile += 16) {
+          const int i0 = (tile / tilesN) << 4, j0 = (tile % tilesN) << 4;
+          acc_t acc = {0, 0, 0, 0};
+          // A = W_k^T (i = c, k = f) = wk[f][c] (masked rows read the zero column C), B = dpre (k = f, j = n)
+          const bool arow = i0 + li < C;
+          acc = tile_mac<T>(acc, wk + lk * Cs1 + (arow ? i0 + li : C), 4 * Cs1, dpre + lk * Ns + j0 + li, 4 * Ns, F4 >> 2);
+          const int n = j0 + li;
+          if (GATED) {
+            const T gx = gvec[n < N ? n : 0], gh = gvec[Ns + (n < N ? n : 0)];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] *= (i0 + Mf<T>::row(lane, r) < G) ? gx : gh;
+          }
+          if (k < K - 1) {
+            // A = acc (i = c, k = m), B = S^T (k = m, j = n) = S[n][m]
+            const T* ap = arow ? ac + (i0 + li) * Ns + lk : zrow + lk;
+            acc = tile_mac<T>(acc, ap, 4, S + (j0 + li) * Ns + lk, 4, N4 >> 2);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = i0 + Mf<T>::row(lane, r);
+            if (c < C && n < N) {
+              if (k > 0) an[c * Ns + n] = acc[r];
+              else if (c < G) dxt[(size_t)c * N + n] = acc[r];
+              else carry[(c - G) * Ns + n] = acc[r];
+            }
+          }
+        }
+        __syncthreads();
+        T* tmp = ac; ac = an; an = tmp;
+      }
+    } else
     for (int k = Kst - 1; k >= 0; --k) {
       T* dst = (k == 0) ? carry : an;
       const T* wk = WBt + (size_t)k * F4 * Fs;
@@ -427,12 +481,13 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
 }
 
 template <typename T>
-size_t dense_bwd_lds(int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, bool gated) {
+size_t dense_bwd_lds(int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, bool gated, bool dx = false) {
   const int K = (int)(Kin > Kst ? Kin : Kst), C = (int)(G + F);
-  const int Ns = lds_stride<T>((int)N), Fs = lds_stride<T>((int)F + 1), Cs = lds_stride<T>(C);
+  const int Ns = lds_stride<T>((int)N), Fs = lds_stride<T>((int)F + 1), Cs = lds_stride<T>(C), Cs1 = lds_stride<T>(C + 1);
   const int F4 = ((int)F + 3) & ~3, C4 = (C + 3) & ~3;
   const int SR = (((int)N + 15) >> 4) * 16;
-  return sizeof(T) * ((size_t)SR * Ns + 2 * (size_t)C4 * Ns + 2 * (size_t)F4 * Ns + (size_t)Kst * F4 * Fs +
+  return sizeof(T) * ((size_t)SR * Ns + 2 * (size_t)C4 * Ns + 2 * (size_t)F4 * Ns +
+                      (dx ? (size_t)K * F4 * Cs1 : (size_t)Kst * F4 * Fs) +
                       (gated ? (size_t)F * K * Cs : 0) + 64 + (size_t)(Ns > K * Cs ? Ns : K * Cs) +
                       (gated ? (2 + 2 * (size_t)(((int)F + 15) >> 4)) * Ns : 0)) + 16;
 }
@@ -462,6 +517,15 @@ extern "C" int gcrnn_small_dense_supported(int dtype, int64_t N, int64_t G, int6
   if (!backward) return tilesF * tilesN <= 16 * 4 && dense_fwd_lds<double>(N, G, F, K) <= DENSE_LDS_MAX;
   return K * tilesF * tilesC <= 16 * 4 && (!gated || tilesF * tilesN <= 32) &&
          dense_bwd_lds<double>(N, G, F, Kin, Kst, gated != 0) <= DENSE_LDS_MAX;
+}
+
+// The backward pass with dX: the predicate of the plain backward, with the LDS image of the DX variant.
+extern "C" int gcrnn_small_dense_backward_dx_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                                       int gated) {
+  if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, 1, gated)) return 0;
+  const size_t lds = dtype == GCRNN_F32 ? dense_bwd_lds<float>(N, G, F, Kin, Kst, gated != 0, true)
+                                        : dense_bwd_lds<double>(N, G, F, Kin, Kst, gated != 0, true);
+  return lds <= DENSE_LDS_MAX ? 1 : 0;
 }
 
 template <typename T>
@@ -497,22 +561,22 @@ extern "C" int gcrnn_small_dense_forward(int dtype, const void* X, const void* h
                                   gate_stride_n, as_stream(stream));
 }
 
-template <typename T, bool GATED>
+template <typename T, bool GATED, bool DX>
 static int dense_bwd_launch(const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
                             const void* bias, const void* gi, const void* gf, const void* Sd, void* pA, void* pB, void* pb,
-                            void* dgi, void* dgf, void* dh0, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
+                            void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
                             int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st) {
-  const size_t lds = dense_bwd_lds<T>(N, G, F, Kin, Kst, GATED);
+  const size_t lds = dense_bwd_lds<T>(N, G, F, Kin, Kst, GATED, DX);
   const int64_t wt = (Kin > Kst ? Kin : Kst) * ((F + 15) / 16) * ((G + F + 15) / 16);   // weight-gradient tiles, persistent
-  auto kern = wt <= 16 ? small_dense_bwd_kernel<T, GATED, 1>
-                       : (wt <= 32 ? small_dense_bwd_kernel<T, GATED, 2> : small_dense_bwd_kernel<T, GATED, 4>);
+  auto kern = wt <= 16 ? small_dense_bwd_kernel<T, GATED, 1, DX>
+                       : (wt <= 32 ? small_dense_bwd_kernel<T, GATED, 2, DX> : small_dense_bwd_kernel<T, GATED, 4, DX>);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
   kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)H, (const T*)dH, (const T*)wA, (const T*)wB,
                                       (const T*)bias, (const T*)gi, (const T*)gf, (const T*)Sd, (T*)pA, (T*)pB, (T*)pb,
-                                      (T*)dgi, (T*)dgf, (T*)dh0, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst, (int)B, gsb,
-                                      gst, gsn);
+                                      (T*)dgi, (T*)dgf, (T*)dh0, (T*)dX, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
+                                      (int)B, gsb, gst, gsn);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -528,9 +592,31 @@ extern "C" int gcrnn_small_dense_backward(int dtype, const void* X, const void* 
   if (B <= 0 || T <= 0 || B > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, 1, gi != nullptr)) return GCRNN_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
+#define GCRNN_DENSE_BWD_ARGS X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, nullptr, B, T, N, G, F, Kin, Kst, \
+                             gate_stride_b, gate_stride_t, gate_stride_n, st
   if (dtype == GCRNN_F32)
-    return gi ? dense_bwd_launch<float, true>(X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t, gate_stride_n, st)
-              : dense_bwd_launch<float, false>(X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t, gate_stride_n, st);
-  return gi ? dense_bwd_launch<double, true>(X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t, gate_stride_n, st)
-            : dense_bwd_launch<double, false>(X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t, gate_stride_n, st);
+    return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);
+  return gi ? dense_bwd_launch<double, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, false>(GCRNN_DENSE_BWD_ARGS);
+#undef GCRNN_DENSE_BWD_ARGS
+}
+
+extern "C" int gcrnn_small_dense_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH,
+                                             const void* wA, const void* wB, const void* bias, const void* gi, const void* gf,
+                                             const void* Sdense, void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0,
+                                             void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                             int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n,
+                                             void* stream) {
+  if (!X || !h0 || !H || !dH || !wA || !wB || !Sdense || !pA || !pB || !pb || !dX) return GCRNN_ERR_NULL_POINTER;
+  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gi != nullptr)) return GCRNN_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+#define GCRNN_DENSE_BWD_ARGS X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
+                             gate_stride_b, gate_stride_t, gate_stride_n, st
+  if (dtype == GCRNN_F32)
+    return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
+  return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
+#undef GCRNN_DENSE_BWD_ARGS
 }

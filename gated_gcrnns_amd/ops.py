@@ -2789,9 +2789,22 @@ def small_training_supported(N, nnz, G, F, Kin, Kst, dtype, E=1):
         lib.gcrnn_small_backward_supported(dtype_code(dtype), int(N), int(nnz), int(G), int(F), int(Kin), int(Kst)))
 
 
+def small_input_grad_supported(N, nnz, G, F, Kin, Kst, dtype, E=1, gated=False, node_gates=False):
+    """The one-launch BPTT kernels also return dX for this shape (their dx variants): small_training_supported, and the family the
+    backward pass runs on takes the variant -- the matrix-core family where its dx image fits in LDS (per-node gates run there only),
+    else the gather family (same LDS image as its plain backward)."""
+    if not small_training_supported(N, nnz, G, F, Kin, Kst, dtype, E):
+        return False
+    if small_dense_supported(N, G, F, Kin, Kst, dtype, backward=True, gated=gated):
+        return bool(lib.gcrnn_small_dense_backward_dx_supported(dtype_code(dtype), int(N), int(G), int(F), int(Kin), int(Kst),
+                                                                int(bool(gated))))
+    return not node_gates
+
+
 class _SmallCell(torch.autograd.Function):
     """Small-graph cell with BPTT: forward = one launch (small_cell_kernel), backward = one launch
-    (small_cell_bwd_kernel). Gradients for the parameters, the time gates and h0; none for X."""
+    (small_cell_bwd_kernel). Gradients for the parameters, the time gates and h0, and -- on the kernels' dx variants, only when
+    X wants one -- for X (small_input_grad_supported)."""
 
     @staticmethod
     def forward(ctx, X, h0, wA, wB, bias, gi, gf, graph):
@@ -2822,11 +2835,26 @@ class _SmallCell(torch.autograd.Function):
             dgi = torch.empty(shape, dtype=dt, device=dev)
             dgf = torch.empty(shape, dtype=dt, device=dev)
         dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+        dX = None
+        if ctx.needs_input_grad[0]:
+            if not small_input_grad_supported(N, fwd.nnz, G, F, Kin, Kst, dt, ctx.graph.E, gated=gi is not None,
+                                              node_gates=gi is not None and not scalar_gates):
+                raise GcrnnError('small_cell_train: no gradient for X at this shape (small_input_grad_supported)')
+            dX = torch.empty_like(X)
         bvec = bias.detach().contiguous().view(-1) if bias is not None else None
         # every operand is a named local: a temporary (dH.contiguous(), a first-use adj.val(dt)) would be released --
         # and its block handed to the next allocation -- before the launch
         dHc, wAc, wBc, fval, aval = dH.contiguous(), wA.contiguous(), wB.contiguous(), fwd.val(dt), adj.val(dt)
-        if dense:
+        if dense and dX is not None:
+            Sd = ctx.graph.dense(dt)
+            gs = _gate_strides(gi, B, T, N)
+            check(lib.gcrnn_small_dense_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
+                                                    _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0),
+                                                    _p(dX), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], _stream()),
+                  'small_dense_backward_dx')
+            if scalar_gates:
+                dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
+        elif dense:
             Sd = ctx.graph.dense(dt)
             gs = _gate_strides(gi, B, T, N)
             check(lib.gcrnn_small_dense_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
@@ -2834,6 +2862,12 @@ class _SmallCell(torch.autograd.Function):
                                                  B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], _stream()), 'small_dense_backward')
             if scalar_gates:                                  # a scalar gate collects the gradients of all its nodes
                 dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
+        elif dX is not None:
+            check(lib.gcrnn_small_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc),
+                                              _p(wBc), _p(bvec), _p(gi), _p(gf), _p(fwd.rowptr), _p(fwd.col),
+                                              _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval), _p(pA), _p(pB), _p(pb),
+                                              _p(dgi), _p(dgf), _p(dh0), _p(dX), B, T, N, G, F, Kin, Kst, fwd.nnz, _stream()),
+                  'small_backward_dx')
         else:
             check(lib.gcrnn_small_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc),
                                            _p(wBc), _p(bvec), _p(gi), _p(gf), _p(fwd.rowptr), _p(fwd.col),
@@ -2843,7 +2877,7 @@ class _SmallCell(torch.autograd.Function):
         dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)
         dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
         db = pb.sum(dim=0).view(F, 1) if bias is not None else None
-        return None, dh0, dwA, dwB, db, dgi, dgf, None
+        return dX, dh0, dwA, dwB, db, dgi, dgf, None
 
 
 def small_cell_train(X, h0, wA, wB, bias, graph, gi=None, gf=None):
@@ -2858,7 +2892,8 @@ def small_gates_supported(N, G, F, Kin, Kst, dtype, backward):
 
 class _SmallTimeGates(torch.autograd.Function):
     """Both time gates of a small-graph cell for all steps: one launch forward, one backward (reference
-    graphML.py:2357-2374). Parameters stacked over (input, forget). Returns gates [2][T][B]. No gradient for X."""
+    graphML.py:2357-2374). Parameters stacked over (input, forget). Returns gates [2][T][B]. The gradient for X (the gate cells read
+    x_t) comes from the backward kernel's dx variant, only when X wants one."""
 
     @staticmethod
     def forward(ctx, X, h0, wA2, wB2, bias2, lw2, lb2, graph):
@@ -2889,10 +2924,17 @@ class _SmallTimeGates(torch.autograd.Function):
         plw = torch.empty((B, 2, F * N), dtype=dt, device=dev)
         plb = torch.empty((B, 2), dtype=dt, device=dev)
         pdh0 = torch.empty((B, 2, F, N), dtype=dt, device=dev) if ctx.needs_input_grad[1] else None
-        check(lib.gcrnn_small_gates_backward(dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(lw2), _p(Sd),
-                                             _p(dsum), _p(pA), _p(pB), _p(pb), _p(plw), _p(plb), _p(pdh0), B, T, N, G, F, Kin,
-                                             Kst, _stream()), 'small_gates_backward')
-        return (None, pdh0.sum(dim=1) if pdh0 is not None else None, pA.sum(dim=0), pB.sum(dim=0),
+        pdX = None
+        if ctx.needs_input_grad[0]:
+            pdX = torch.empty((B, 2, T, G, N), dtype=dt, device=dev)
+            check(lib.gcrnn_small_gates_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(lw2), _p(Sd),
+                                                    _p(dsum), _p(pA), _p(pB), _p(pb), _p(plw), _p(plb), _p(pdh0), _p(pdX), B, T, N,
+                                                    G, F, Kin, Kst, _stream()), 'small_gates_backward_dx')
+        else:
+            check(lib.gcrnn_small_gates_backward(dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(lw2), _p(Sd),
+                                                 _p(dsum), _p(pA), _p(pB), _p(pb), _p(plw), _p(plb), _p(pdh0), B, T, N, G, F, Kin,
+                                                 Kst, _stream()), 'small_gates_backward')
+        return (pdX[:, 0] + pdX[:, 1] if pdX is not None else None, pdh0.sum(dim=1) if pdh0 is not None else None, pA.sum(dim=0), pB.sum(dim=0),
                 pb.sum(dim=0) if bias2 is not None else None, plw.sum(dim=0), plb.sum(dim=0) if ctx.has_lb else None, None)
 
 

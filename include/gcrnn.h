@@ -675,13 +675,21 @@ int gcrnn_small_forward(int dtype, const void* X, const void* h0, const void* wA
  * graph PyTorch records for the T-step loop). H = forward output, dH = gradient w.r.t. every state [B][T][F][N];
  * CSR(S^T) (rowptr/col/val) and CSR(S) (arowptr/acol/aval). Per-sequence partial sums, to be added over the first two
  * dimensions by the caller in a fixed order:  pA [B][2][F][Kin][G], pB [B][2][F][Kst][F], pb [B][F];
- * dgi / dgf [T][B] (time-gated cells, else NULL); dh0 [B][F][N] or NULL. dX is not produced. */
+ * dgi / dgf [T][B] (time-gated cells, else NULL); dh0 [B][F][N] or NULL. gcrnn_small_backward produces no dX;
+ * gcrnn_small_backward_dx is the same pass with the input gradient dX [B][T][G][N] as well (required): with z = [x | h] the
+ * adjoint dX_t = sum_k (A_k^T (gi_t dpre_t)) (S^T)^k shares one Horner chain over G + F channels with the carry. Same LDS image,
+ * so gcrnn_small_backward_supported answers for both. Deterministic (no atomics). */
 int gcrnn_small_backward_supported(int dtype, int64_t N, int64_t nnz, int64_t G, int64_t F, int64_t Kin, int64_t Kst);
 int gcrnn_small_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
                          const void* wB, const void* bias, const void* gi, const void* gf, const int32_t* rowptr,
                          const int32_t* col, const void* val, const int32_t* arowptr, const int32_t* acol, const void* aval,
                          void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0, int64_t B, int64_t T, int64_t N,
                          int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz, void* stream);
+int gcrnn_small_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                            const void* wB, const void* bias, const void* gi, const void* gf, const int32_t* rowptr,
+                            const int32_t* col, const void* val, const int32_t* arowptr, const int32_t* acol, const void* aval,
+                            void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T,
+                            int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz, void* stream);
 
 /* Same contract on the matrix cores for graphs whose DENSE N x N GSO fits in LDS (the drivers' N = 50..80): every hop,
  * tap, weight-gradient and adjoint product of a time step is a small GEMM on v_mfma_f64_16x16x4_f64 /
@@ -690,7 +698,10 @@ int gcrnn_small_backward(int dtype, const void* X, const void* h0, const void* H
  * every node; element (b, t, n) is read at b * gate_stride_b + t * gate_stride_t + n * gate_stride_n, so [T][B] time gates
  * (strides 1, B, 0), [B][T][N] node gates (graphML.py:2379-2407) or their product (strides T N, N, 1) need no copy; both
  * NULL = un-gated. backward: pA [B][F][Kin][G], pB [B][F][Kst][F], pb [B][F] per-sequence partial sums (added over B by the
- * caller), dgi / dgf [B][T][N] (dense; a scalar gate's gradient is their sum over n), dh0 [B][F][N] or NULL. */
+ * caller), dgi / dgf [B][T][N] (dense; a scalar gate's gradient is their sum over n), dh0 [B][F][N] or NULL.
+ * gcrnn_small_dense_backward_dx: the same pass with dX [B][T][G][N] as well (required); the adjoint filter of the input taps is fed
+ * gi . dpre_t per node, so node-gated cells are covered. Its LDS image holds the taps of both filters for the adjoint chain, so it
+ * has a query of its own: gcrnn_small_dense_backward_dx_supported implies gcrnn_small_dense_supported(..., backward = 1, gated). */
 int gcrnn_small_dense_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int backward,
                                 int gated);
 int gcrnn_small_dense_forward(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
@@ -702,13 +713,21 @@ int gcrnn_small_dense_backward(int dtype, const void* X, const void* h0, const v
                                void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0, int64_t B, int64_t T,
                                int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
                                int64_t gate_stride_t, int64_t gate_stride_n, void* stream);
+int gcrnn_small_dense_backward_dx_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int gated);
+int gcrnn_small_dense_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                                  const void* wB, const void* bias, const void* gi, const void* gf, const void* Sdense,
+                                  void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T,
+                                  int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                  int64_t gate_stride_t, int64_t gate_stride_n, void* stream);
 
 /* Time gates of the small-graph regime (GGCRNNCell time gating, graphML.py:2248-2278, 2357-2374), both gates in one launch:
  *   gate[g][t][b] = sigmoid( lw_g . vec_{F,N}( tanh(A_g(S) x_t + B_g(S) h0 + 2 b_g) ) + lb_g ),  g = 0 input, 1 forget.
  * Parameters stacked over the two gates: wA2 [2][F][Kin][G], wB2 [2][F][Kst][F], bias2 [2][F] or NULL, lw2 [2][F*N]
  * (nn.Linear weight, row-major over (f, n)), lb2 [2] or NULL. backward: dsum [2][T][B] = d loss / d (pre-sigmoid value);
  * per-sequence partial sums pA [B][2][F][Kin][G], pB [B][2][F][Kst][F], pb [B][2][F], plw [B][2][F*N], plb [B][2],
- * pdh0 [B][2][F][N] (or NULL). */
+ * pdh0 [B][2][F][N] (or NULL). gcrnn_small_gates_backward_dx: the same pass with each gate's share of the input gradient as well,
+ * pdX [B][2][T][G][N] (required; the gate cells read x_t through A_g(S)); the caller adds the two gates in a fixed order. Same LDS
+ * image: gcrnn_small_gates_supported(..., backward = 1) answers for both. */
 int gcrnn_small_gates_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int backward);
 int gcrnn_small_gates_forward(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2,
                               const void* lw2, const void* lb2, const void* Sdense, void* gate, int64_t B, int64_t T,
@@ -717,6 +736,10 @@ int gcrnn_small_gates_backward(int dtype, const void* X, const void* h0, const v
                                const void* lw2, const void* Sdense, const void* dsum, void* pA, void* pB, void* pb, void* plw,
                                void* plb, void* pdh0, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
                                int64_t Kst, void* stream);
+int gcrnn_small_gates_backward_dx(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2,
+                                  const void* lw2, const void* Sdense, const void* dsum, void* pA, void* pB, void* pb, void* plw,
+                                  void* plb, void* pdh0, void* pdX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
+                                  int64_t Kin, int64_t Kst, void* stream);
 
 /* EDGE-gated cell of the small-graph regime (spatial_gating = 'edge', graphML.py:2411-2416 with graphAttention, graphML.py:521-627;
  * one head, one edge feature, concatenated, ReLU), inference: h_t = tanh(gi_t att_in(A(S) x_t + b) + gf_t att_f(B(S) h_{t-1} + b)).
