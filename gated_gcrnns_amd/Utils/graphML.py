@@ -688,16 +688,21 @@ class GGCRNNCell(nn.Module):
         return dt in (torch.float32, torch.float64) and h0.dtype == dt and all(p.dtype == dt for p in self.parameters())
 
     def _use_small_edge_training(self, X, h0):
-        """Edge-gated cell on a small graph, gradients wanted for parameters / h0 but not for X: the forward of _use_small_edge with every
-        state kept, BPTT in two launches (ops.small_edge_cell_train). GCRNN_NO_SMALL_EDGE=1 switches this path off too."""
-        if not torch.is_grad_enabled() or X.requires_grad:
+        """Edge-gated cell on a small graph, gradients wanted for parameters / h0: the forward of _use_small_edge with every state kept,
+        BPTT in two launches (ops.small_edge_cell_train). An X that wants a gradient takes this path only with GCRNN_SMALL_EDGE_DX=1 (read
+        at every forward; the kernels' dx variant, ops.small_edge_input_grad_supported) and then counts as wanting one even where nothing
+        else does; without the variable it stays on the composed path. GCRNN_NO_SMALL_EDGE=1 switches this path off in either case."""
+        if not torch.is_grad_enabled():
             return False
-        if not (h0.requires_grad or any(p.requires_grad for p in self.parameters())):
+        x_grad = X.requires_grad
+        if x_grad and not os.environ.get('GCRNN_SMALL_EDGE_DX'):
+            return False
+        if not (x_grad or h0.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
         if not self._small_edge_takes(X, h0):
             return False
-        return ops.small_edge_training_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin,
-                                                 self.Kst, X.dtype, self.E)
+        supported = ops.small_edge_input_grad_supported if x_grad else ops.small_edge_training_supported
+        return supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin, self.Kst, X.dtype, self.E)
 
     def _forward_small_edge(self, X, h0, last_only=False, train=False):
         assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N

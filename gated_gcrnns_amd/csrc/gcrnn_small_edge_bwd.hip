@@ -10,7 +10,9 @@
 //   softmax^T:       de[q] = p[q] - alpha[q] sum_{row m_q} p,  dzz = de (zz >= 0 ? 1 : 0.2),  ds1[n] = sum_{column n} dzz,  ds2[m] = sum_{row m} dzz
 //   folded taps^T:   dwf[r][k][c] += sum_n dwx[r][n] z_k[c][n],  dbf[r] += sum_n dwx[r][n]   (dwx = dWx | ds1 | ds2; registers, all t)
 //   hops^T (Horner): g_{K-1} = dz_{K-1},  g_{k-1} = dz_{k-1} + g_k S^T  with  dz_k[c][n] = sum_r wf[r][k][c] dwx[r][n];  dh <- g_0
-// XP = true, one workgroup per (b, t): the same from x_t with dPre[b][t] as upstream and the gate gi; no hop adjoint (no gradient for X).
+// XP = true, one workgroup per (b, t): the same from x_t with dPre[b][t] as upstream and the gate gi. Without DX it ends at the folded
+//   taps' adjoint (no gradient for X). With DX (XP only) the hops' adjoint runs here too, on the C = G channels with K = Kin, and its
+//   g_0 is dX[b][t]; gi_t is already inside dy, so nothing more is scaled. K = 1 has no hop: dX = dz_0.
 // Row-ordered sums walk the support rows through `inv`, the inverse of the permutation t_pos (row position of column-ordered edge q).
 // The gradients of the FOLDED taps and bias leave in per-workgroup slots; the host side sums the slots and unfolds them.
 // No atomics, every sum in a fixed order: bit-reproducible, and a sequence's results do not depend on the rest of the batch.
@@ -36,7 +38,7 @@ template <typename T> __device__ __forceinline__ T seb_group_sum(T v) {
 
 }  // namespace
 
-template <typename T, bool XP>
+template <typename T, bool XP, bool DX = false>
 __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     const T* __restrict__ U,          // XP: X [B][Tn][C][N]        else: h0 [B][C][N]  (C = F)
     const T* __restrict__ Hs,         // [B][Tn][F][N] states of the forward (not XP)
@@ -47,15 +49,17 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     const T* __restrict__ attA,       // [2 F]  a1 | a2
     const T* __restrict__ gate,       // [Tn][B] or null            XP: gi, else: gf
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const T* __restrict__ val,          // CSR(S^T)
-    const int32_t* __restrict__ a_rowptr, const int32_t* __restrict__ a_col, const T* __restrict__ a_val,    // CSR(S) (not XP)
+    const int32_t* __restrict__ a_rowptr, const int32_t* __restrict__ a_col, const T* __restrict__ a_val,    // CSR(S) (not XP, or DX)
     const int32_t* __restrict__ s_rowptr, const int2* __restrict__ r_edge,
     const int32_t* __restrict__ t_rowptr, const int2* __restrict__ t_edge, const T* __restrict__ t_val, const int32_t* __restrict__ t_pos,
     T* __restrict__ dPre,             // [B][Tn][F][N]              XP: read, else: written
     T* __restrict__ pwf,              // [gridDim.x][R][K][C] gradient of the folded taps
     T* __restrict__ pbf,              // [gridDim.x][R]       ... and of the folded bias
     T* __restrict__ dgate,            // [Tn][B] or null (with gate)
-    T* __restrict__ dh0,              // [B][F][N] or null (not XP)
+    T* __restrict__ dU,               // XP with DX: dX [B][Tn][C][N]   not XP: dh0 [B][F][N] or null
     int Tn, int N, int C, int F, int K, int nnz, int nnzs, int B) {
+  static_assert(XP || !DX, "the gradient for X leaves the input branch");
+  constexpr bool HOPS = !XP || DX;                           // the hops' adjoint runs: CSR(S) in LDS
   extern __shared__ __attribute__((aligned(16))) char smem_small_edge_bwd[];
   const int R = F + 2;
   const int KC = K * C, CN = C * N, FN = F * N, RN = R * N;
@@ -94,7 +98,7 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
 
   for (int i = tid; i < nnz; i += SEB_THREADS) {
     vall[i] = val[i]; coll[i] = col[i];
-    if (!XP) { avl[i] = a_val[i]; acl[i] = a_col[i]; }
+    if (HOPS) { avl[i] = a_val[i]; acl[i] = a_col[i]; }
   }
   for (int i = tid; i < nnzs; i += SEB_THREADS) {
     tvl[i] = t_val[i]; rcol[i] = r_edge[i].x; tm[i] = t_edge[i].x;
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
   }
   for (int i = tid; i <= N; i += SEB_THREADS) {
     rpl[i] = rowptr[i]; rrp[i] = s_rowptr[i]; trp[i] = t_rowptr[i];
-    if (!XP) arp[i] = a_rowptr[i];
+    if (HOPS) arp[i] = a_rowptr[i];
   }
   // fold the attention's mixing matrix and mixer into the taps, as the forward does
   for (int i = tid; i < F * KC; i += SEB_THREADS) {
@@ -329,8 +333,8 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
         dwacc[p] += acc;
       }
     }
-    if (!XP) {
-      // -------------------------------------------------------------- adjoint of the hops, Horner form; the last one is the new dh
+    if (HOPS) {
+      // -------------------------------------------------------------- adjoint of the hops, Horner form; g_0 is the new dh (DX: dX_t)
       const T* src = nullptr;
       for (int k = K - 1; k >= 0; --k) {
         T* dst = oth;
@@ -351,6 +355,10 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
         oth = cur;
         cur = dst;
       }
+      if (DX) {
+        T* dx = dU + ((size_t)b * Tn + t) * CN;
+        for (int i = tid; i < CN; i += SEB_THREADS) dx[i] = cur[i];
+      }
     } else {
       __syncthreads();
     }
@@ -364,8 +372,8 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
       else pbf[(size_t)blockIdx.x * R + r] = dwacc[p];
     }
   }
-  if (!XP && dh0)
-    for (int i = tid; i < FN; i += SEB_THREADS) dh0[(size_t)b * FN + i] = cur[i];
+  if (!XP && dU)
+    for (int i = tid; i < FN; i += SEB_THREADS) dU[(size_t)b * FN + i] = cur[i];
 }
 
 static size_t small_edge_bwd_lds_bytes(int dtype, int64_t N, int64_t nnz, int64_t nnzs, int64_t G, int64_t F, int64_t Kin, int64_t Kst) {
@@ -387,16 +395,16 @@ extern "C" int gcrnn_small_edge_backward_supported(int dtype, int64_t N, int64_t
   return small_edge_bwd_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst) <= 150 * 1024 ? 1 : 0;
 }
 
-template <typename T>
+template <typename T, bool DX>
 static int small_edge_bwd_launch(const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
                                  const void* bias, const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a,
                                  const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col, const void* val,
                                  const int32_t* a_rowptr, const int32_t* a_col, const void* a_val, const int32_t* s_rowptr,
                                  const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val,
                                  const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf,
-                                 void* dh0, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                 void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
                                  int64_t nnz, int64_t nnzs, size_t lds, hipStream_t st) {
-  auto kx = small_edge_bptt_kernel<T, true>;
+  auto kx = small_edge_bptt_kernel<T, true, DX>;
   auto kh = small_edge_bptt_kernel<T, false>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -407,26 +415,29 @@ static int small_edge_bwd_launch(const void* X, const void* h0, const void* H, c
                                             (const T*)a_val, s_rowptr, (const int2*)r_edge, t_rowptr, (const int2*)t_edge,
                                             (const T*)t_val, t_pos, (T*)dPre, (T*)pwfB, (T*)pbfB, (T*)dgf, (T*)dh0, (int)Tn, (int)N,
                                             (int)F, (int)F, (int)Kst, (int)nnz, (int)nnzs, (int)B);
+  // the input branch reads CSR(S) only for dX
   kx<<<(unsigned)(B * Tn), SEB_THREADS, lds, st>>>((const T*)X, (const T*)nullptr, (const T*)nullptr, (const T*)wA, (const T*)bias,
                                                    (const T*)att_in_w, (const T*)att_in_a, (const T*)gi, rowptr, col, (const T*)val,
-                                                   nullptr, nullptr, (const T*)nullptr, s_rowptr, (const int2*)r_edge, t_rowptr,
-                                                   (const int2*)t_edge, (const T*)t_val, t_pos, (T*)dPre, (T*)pwfA, (T*)pbfA, (T*)dgi,
-                                                   (T*)nullptr, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)nnz, (int)nnzs, (int)B);
+                                                   DX ? a_rowptr : nullptr, DX ? a_col : nullptr, DX ? (const T*)a_val : nullptr,
+                                                   s_rowptr, (const int2*)r_edge, t_rowptr, (const int2*)t_edge, (const T*)t_val, t_pos,
+                                                   (T*)dPre, (T*)pwfA, (T*)pbfA, (T*)dgi, DX ? (T*)dX : (T*)nullptr, (int)Tn, (int)N,
+                                                   (int)G, (int)F, (int)Kin, (int)nnz, (int)nnzs, (int)B);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
 
-extern "C" int gcrnn_small_edge_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
-                                         const void* wB, const void* bias, const void* att_in_w, const void* att_in_a,
-                                         const void* att_f_w, const void* att_f_a, const void* gi, const void* gf,
-                                         const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* a_rowptr,
-                                         const int32_t* a_col, const void* a_val, const int32_t* s_rowptr, const int32_t* r_edge,
-                                         const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val, const int32_t* t_pos,
-                                         void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf, void* dh0,
-                                         int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz,
-                                         int64_t nnz_support, void* stream) {
+// both entry points: the validation, then the two launches; DX: dX is one more required pointer
+template <bool DX>
+static int small_edge_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
+                               const void* bias, const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a,
+                               const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col, const void* val,
+                               const int32_t* a_rowptr, const int32_t* a_col, const void* a_val, const int32_t* s_rowptr,
+                               const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val,
+                               const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf,
+                               void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                               int64_t nnz, int64_t nnz_support, void* stream) {
   if (!X || !h0 || !H || !dH || !wA || !wB || !att_in_w || !att_in_a || !att_f_w || !att_f_a || !rowptr || !a_rowptr || !s_rowptr ||
-      !t_rowptr || !dPre || !pwfA || !pbfA || !pwfB || !pbfB)
+      !t_rowptr || !dPre || !pwfA || !pbfA || !pwfB || !pbfB || (DX && !dX))
     return GCRNN_ERR_NULL_POINTER;
   if ((nnz > 0 && (!col || !val || !a_col || !a_val)) || (nnz_support > 0 && (!r_edge || !t_edge || !t_val || !t_pos)))
     return GCRNN_ERR_NULL_POINTER;
@@ -438,10 +449,40 @@ extern "C" int gcrnn_small_edge_backward(int dtype, const void* X, const void* h
   if (!gcrnn_small_edge_backward_supported(dtype, N, nnz, nnz_support, G, F, Kin, Kst)) return GCRNN_ERR_UNSUPPORTED;
   const size_t lds = small_edge_bwd_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst);
   if (dtype == GCRNN_F32)
-    return small_edge_bwd_launch<float>(X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
-                                        a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA,
-                                        pwfB, pbfB, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, nnz, nnz_support, lds, as_stream(stream));
-  return small_edge_bwd_launch<double>(X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
-                                       a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA,
-                                       pwfB, pbfB, dgi, dgf, dh0, B, T, N, G, F, Kin, Kst, nnz, nnz_support, lds, as_stream(stream));
+    return small_edge_bwd_launch<float, DX>(X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
+                                            a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA,
+                                            pwfB, pbfB, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, lds,
+                                            as_stream(stream));
+  return small_edge_bwd_launch<double, DX>(X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
+                                           a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA,
+                                           pwfB, pbfB, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, lds,
+                                           as_stream(stream));
+}
+
+extern "C" int gcrnn_small_edge_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                                         const void* wB, const void* bias, const void* att_in_w, const void* att_in_a,
+                                         const void* att_f_w, const void* att_f_a, const void* gi, const void* gf,
+                                         const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* a_rowptr,
+                                         const int32_t* a_col, const void* a_val, const int32_t* s_rowptr, const int32_t* r_edge,
+                                         const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val, const int32_t* t_pos,
+                                         void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf, void* dh0,
+                                         int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz,
+                                         int64_t nnz_support, void* stream) {
+  return small_edge_backward<false>(dtype, X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
+                                    a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB,
+                                    pbfB, dgi, dgf, dh0, nullptr, B, T, N, G, F, Kin, Kst, nnz, nnz_support, stream);
+}
+
+extern "C" int gcrnn_small_edge_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                                            const void* wB, const void* bias, const void* att_in_w, const void* att_in_a,
+                                            const void* att_f_w, const void* att_f_a, const void* gi, const void* gf,
+                                            const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* a_rowptr,
+                                            const int32_t* a_col, const void* a_val, const int32_t* s_rowptr, const int32_t* r_edge,
+                                            const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val, const int32_t* t_pos,
+                                            void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf, void* dh0,
+                                            void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                            int64_t nnz, int64_t nnz_support, void* stream) {
+  return small_edge_backward<true>(dtype, X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
+                                   a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB,
+                                   pbfB, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, stream);
 }

@@ -3003,6 +3003,12 @@ def small_edge_training_supported(N, nnz, nnz_support, G, F, Kin, Kst, dtype, E=
                                                         int(Kin), int(Kst)))
 
 
+def small_edge_input_grad_supported(N, nnz, nnz_support, G, F, Kin, Kst, dtype, E=1):
+    """The edge-gated BPTT also returns dX: the same answer as small_edge_training_supported (the backward kernels' LDS image is sized for
+    max(G, F) channels in both launches, so the input branch's hop adjoint adds nothing). The counterpart of small_input_grad_supported."""
+    return small_edge_training_supported(N, nnz, nnz_support, G, F, Kin, Kst, dtype, E)
+
+
 def _edge_unfold(pwf, pbf, w, bias, mixer, weight):
     """Gradients of one branch's taps w [F][1][K][C], bias, attention mixer and weight from the per-workgroup gradients of the folded
     taps wf = [W w ; a1^T W w ; a2^T W w] (pwf [slots][F+2][K][C]) and of the folded bias (pbf [slots][F+2])."""
@@ -3025,7 +3031,8 @@ def _edge_unfold(pwf, pbf, w, bias, mixer, weight):
 class _SmallEdgeCell(torch.autograd.Function):
     """Edge-gated small-graph cell with BPTT: forward = the two launches of the inference path (all states kept), backward = two launches
     (small_edge_bptt_kernel, recurrence then input branch) plus the unfolding of the folded taps' gradients. Gradients for h0, the taps, the
-    bias, both attentions' mixer and weight and the time gates; none for X."""
+    bias, both attentions' mixer and weight and the time gates; for X too when it wants one (the input-branch launch's dx variant, which
+    goes on to the hops' adjoint; no launch is added)."""
 
     @staticmethod
     def forward(ctx, X, h0, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf, graph):
@@ -3056,31 +3063,39 @@ class _SmallEdgeCell(torch.autograd.Function):
             dgi = torch.empty((T, B), dtype=dt, device=dev)
             dgf = torch.empty((T, B), dtype=dt, device=dev)
         dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+        dX = torch.empty_like(X) if ctx.needs_input_grad[0] else None
         bvec = bias.contiguous().view(-1) if bias is not None else None
         # every operand is a named local (see _SmallCell.backward)
         dHc, wAc, wBc = dH.contiguous(), wA.contiguous(), wB.contiguous()
         wi, ai, wfo, afo = w_in.contiguous(), m_in.contiguous(), w_f.contiguous(), m_f.contiguous()
         fval, aval, tvals = fwd.val(dt), adj.val(dt), _edge_support_values(graph, dt)
-        check(lib.gcrnn_small_edge_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
-                                            _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
-                                            _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
-                                            _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']),
-                                            _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB),
-                                            _p(dgi), _p(dgf), _p(dh0), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs, _stream()),
-              'small_edge_backward')
+        if dX is not None:
+            check(lib.gcrnn_small_edge_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
+                                                   _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
+                                                   _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
+                                                   _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']),
+                                                   _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB),
+                                                   _p(dgi), _p(dgf), _p(dh0), _p(dX), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs,
+                                                   _stream()), 'small_edge_backward_dx')
+        else:
+            check(lib.gcrnn_small_edge_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
+                                                _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
+                                                _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
+                                                _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']),
+                                                _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB),
+                                                _p(dgi), _p(dgf), _p(dh0), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs, _stream()),
+                  'small_edge_backward')
         dwA, dbA, dm_in, dw_in = _edge_unfold(pwfA, pbfA, wAc, bias, ai, wi)
         dwB, dbB, dm_f, dw_f = _edge_unfold(pwfB, pbfB, wBc, bias, afo, wfo)
         db = dbA + dbB if bias is not None else None              # one bias, both branches
-        return None, dh0, dwA, dwB, db, dm_in, dw_in, dm_f, dw_f, dgi, dgf, None
+        return dX, dh0, dwA, dwB, db, dm_in, dw_in, dm_f, dw_f, dgi, dgf, None
 
 
 def small_edge_cell_train(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, gf=None):
     """Training forward of the edge-gated small-graph cell (small_edge_training_supported shapes). att_in / att_f: (mixer, weight) of the
-    input / forget attention; gi / gf: differentiable time gates [T][B] or None. Gradients for everything but X: an X that wants one is
-    an error here (the module keeps the composed path for it), not a silent None."""
+    input / forget attention; gi / gf: differentiable time gates [T][B] or None. Gradients for everything that wants one, X included
+    (small_edge_input_grad_supported: the same shapes); an X without requires_grad costs nothing extra."""
     require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1])
-    if X.requires_grad and torch.is_grad_enabled():
-        raise GcrnnError('small_edge_cell_train: no gradient for X on this path (detach X, or use the composed path)')
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
     if not small_edge_training_supported(N, graph.fwd[0].nnz, graph.edge_plan()['nnz'], G, F, Kin, Kst, X.dtype, graph.E):

@@ -762,14 +762,18 @@ int gcrnn_small_edge_forward(int dtype, const void* X, const void* h0, const voi
 /* Training half of the edge-gated small-graph cell: BPTT of gcrnn_small_edge_forward (last_only = 0) from its states H alone -- every
  * step's intermediates are recomputed from h_{t-1} / x_t. Two launches whatever T is: one workgroup per sequence walks t = T-1 .. 0 and
  * leaves dpre_t = (dH_t + dh)(1 - h_t^2) in the scratch dPre [B][T][F][N]; then one workgroup per (b, t) back-propagates the input branch.
- * No gradient for X. Graph operands as gcrnn_small_edge_forward plus CSR(S) (a_rowptr / a_col / a_val, the hops' adjoint) and t_pos
+ * Graph operands as gcrnn_small_edge_forward plus CSR(S) (a_rowptr / a_col / a_val, the hops' adjoint) and t_pos
  * [nnz_support] = the position of column-list edge q in the row lists (a permutation).
  * Outputs are the gradients of the FOLDED taps, rows f < F = W w, rows F, F + 1 = a1^T W w, a2^T W w (bias likewise), as per-workgroup
  * partial sums to be added over the leading axis: pwfA [B*T][F+2][Kin][G], pbfA [B*T][F+2], pwfB [B][F+2][Kst][F], pbfB [B][F+2];
  * dgi / dgf [T][B] (with gi / gf, else NULL); dh0 [B][F][N] or NULL. No atomics: bit-reproducible, batch-independent.
+ * gcrnn_small_edge_backward gives no gradient for X. gcrnn_small_edge_backward_dx is the same call with one more required pointer
+ * after dh0, dX [B][T][G][N]: its input-branch launch goes on to the adjoint of the hops (Horner, over the G input channels with Kin
+ * taps), summed in a fixed order like everything else; same validation order and status codes.
  * supported: gcrnn_small_edge_supported, (F + 2) (max(Kin, Kst) max(G, F) + 1) <= 4096 and, with e = sizeof(dtype), K = max(Kin, Kst),
  * C = max(G, F), R = F + 2:  e (K C N + R K C + R + 2 R N + 3 N + 3 nnz_support + 2 nnz + 2 C N + 16)
- *                            + 4 (4 (N + 1) + 2 nnz + 4 nnz_support) + 16  <=  150 KiB of LDS. */
+ *                            + 4 (4 (N + 1) + 2 nnz + 4 nnz_support) + 16  <=  150 KiB of LDS.
+ * That image is sized for max(G, F) channels in both launches, so the query answers for both entry points: there is no separate one. */
 int gcrnn_small_edge_backward_supported(int dtype, int64_t N, int64_t nnz, int64_t nnz_support, int64_t G, int64_t F, int64_t Kin,
                                         int64_t Kst);
 int gcrnn_small_edge_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
@@ -780,6 +784,14 @@ int gcrnn_small_edge_backward(int dtype, const void* X, const void* h0, const vo
                               const void* t_val, const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB,
                               void* dgi, void* dgf, void* dh0, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
                               int64_t Kst, int64_t nnz, int64_t nnz_support, void* stream);
+int gcrnn_small_edge_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
+                                 const void* wB, const void* bias, const void* att_in_w, const void* att_in_a, const void* att_f_w,
+                                 const void* att_f_a, const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col,
+                                 const void* val, const int32_t* a_rowptr, const int32_t* a_col, const void* a_val,
+                                 const int32_t* s_rowptr, const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge,
+                                 const void* t_val, const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB,
+                                 void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
+                                 int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support, void* stream);
 
 /* ==== per-node output head=========================================================================================
  * mlpType = 'multipMlp' of GatedGCRNNforRegression (architectures.py:1616-1627: one Linear(F -> O) applied to every node's

@@ -5,6 +5,11 @@ training path (ops.small_edge_cell_train: two launches forward, two backward) ag
 in the same process (GCRNN_NO_SMALL_EDGE=1, the path every tree before these kernels takes); step time and kernel launches per step.
 
     python tools/small_edge_train_bench.py [--reps 5] [--iters 20] [--settle-ms 100] [--out profiles/small_edge_train_bench.jsonl]
+    python tools/small_edge_train_bench.py --x-grad [...] [--out profiles/small_edge_input_grad_bench.jsonl]
+
+--x-grad: the step's X requires a gradient (a stacked cell, an encoder in front, saliency). New path: GCRNN_SMALL_EDGE_DX=1 (the BPTT
+kernels' dx variant, ops.small_edge_input_grad_supported); composed path: the variable unset, which is what the module does by default
+and what every tree before the dx variant does. X.grad is part of the compared gradients.
 
 What is timed: a host clock around `iters` back-to-back steps ending in a device synchronise, divided by iters; `reps` such
 measurements per path, INTERLEAVED (composed, new, composed, new, ...), each behind untimed steps for --settle-ms (the clock
@@ -33,6 +38,7 @@ SHAPES = {'epicenter_adj59': ('g5_cls_T20K4_none.npz', 4), 'kstep_sbm50': ('g5_r
 STEPS = (5, 20, 200)
 DTYPES = {'f32': torch.float32, 'f64': torch.float64}
 SWITCH = 'GCRNN_NO_SMALL_EDGE'
+DX_SWITCH = 'GCRNN_SMALL_EDGE_DX'
 
 
 def settle(fn, ms):
@@ -61,16 +67,16 @@ def launches(fn):
     return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
 
 
-def with_switch(on, fn):
+def with_switch(on, fn, name=SWITCH):
     def run():
         if on:
-            os.environ[SWITCH] = '1'
+            os.environ[name] = '1'
         else:
-            os.environ.pop(SWITCH, None)
+            os.environ.pop(name, None)
         try:
             return fn()
         finally:
-            os.environ.pop(SWITCH, None)
+            os.environ.pop(name, None)
     return run
 
 
@@ -92,12 +98,15 @@ def main(argv=None):
     ap.add_argument('--settle-ms', type=float, default=100.0)
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--commit', default=None)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'small_edge_train_bench.jsonl'))
+    ap.add_argument('--x-grad', action='store_true', help='X requires a gradient; new path = GCRNN_SMALL_EDGE_DX=1, composed = unset')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'small_edge_input_grad_bench.jsonl' if args.x_grad else 'small_edge_train_bench.jsonl')
     assert torch.cuda.is_available(), 'small_edge_train_bench needs a ROCm device: a CPU timing says nothing about the GPU'
     dev = torch.device('cuda:0')
     rev = args.commit or commit()
-    has_new = hasattr(ops, 'small_edge_cell_train')
+    has_new = hasattr(ops, 'small_edge_input_grad_supported' if args.x_grad else 'small_edge_cell_train')
     lines = []
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for sname, (fixture, K) in SHAPES.items():
@@ -114,17 +123,25 @@ def main(argv=None):
                     X = torch.randn(args.batch, T, 1, N, generator=g).to(dev, dt)
                     h0 = torch.zeros(args.batch, 20, N, dtype=dt, device=dev)
                     params = list(cell.parameters())
+                    if args.x_grad:
+                        params.append(X.requires_grad_())
 
                     def step():
                         for p in params:
                             p.grad = None
                         cell(X, h0).sum().backward()
                         return params
-                    paths = {'composed': with_switch(True, step)}
-                    if has_new:
-                        paths['new'] = with_switch(False, step)
+                    if args.x_grad:
+                        os.environ.pop(SWITCH, None)
+                        paths = {'composed': with_switch(False, step, DX_SWITCH)}
+                        if has_new:
+                            paths['new'] = with_switch(True, step, DX_SWITCH)
+                    else:
+                        paths = {'composed': with_switch(True, step)}
+                        if has_new:
+                            paths['new'] = with_switch(False, step)
                     line = dict(shape=sname, N=N, F=20, K=K, G=1, B=args.batch, T=T, dtype=dname, cell='time_edge' if tg else 'edge',
-                                reps=args.reps, iters=args.iters, settle_ms=args.settle_ms, commit=rev)
+                                reps=args.reps, iters=args.iters, settle_ms=args.settle_ms, commit=rev, **({'x_grad': True} if args.x_grad else {}))
                     times = {k: [] for k in paths}
                     for k, fn in paths.items():
                         for _ in range(3):
