@@ -18,6 +18,10 @@
 //    chunk's epilogue, so the step boundary waits for nothing that was not already on its way.
 //  * LDS: planes / transposed user-layout tile 66 KB | ONE chunk's weight fragments K*KS*2 KB (the next chunk's arrive by LDS-DMA
 //    during the epilogue) | column words | a 128-node inline-pack tile (8 rounds per step, one per hop at K = 5).
+//    At START-UP (self-start, VAR 7 or 13 with Seq32Args::self_start; before the tables, the weights and the first seed): bytes [0, 64 KB) -- the
+//    two planes, below the bias table -- are a staging area of 32 feature rows x 1024 nodes x 2 B (pitch 2 KB, the 16-byte pieces of row R
+//    rotated by 2 (R >> 3) places) that whole 32-feature k-steps of the USER-layout h0 and x_0 pass through on their way into the operand
+//    registers, then G rows x RPH * 128 nodes of x_1 on their way into the sequence-major work buffer.
 // Arithmetic differs from the 16-feature kernels only in rounding (w^k W_k rounded to bf16 instead of W_k, sums before taps), so this
 // kernel is pinned to the fp64 oracle directly (tests/test_fused.py), not bit-compared with them.
 //
@@ -145,6 +149,10 @@ struct Seq32Args {
   // VAR bit 3 (output head Linear(F -> 1) shared by all nodes, evaluated on the packed state in the epilogue; no user-layout output):
   const float* head_w; const float* head_b;            // [F] fp32, one fp32 on the device (or null)
   float* y0;                                           // y [B][nsteps][N] fp32
+  // Self-start (VAR 7 and 13, MODE 0, un-gated; wave-uniform runtime switch: the code sits outside the step loop): the first operand
+  // [h0 | x_0] of a sequence comes from the USER-layout tensors h0u [B][F][N] and pk_src0 (X[b][0]); step 0 lays out x_1. x0 / pk_dst0 is
+  // then a work buffer of this launch (slot 0 is never touched), hfirst is not read.
+  const uint16_t* h0u; int self_start;
 };
 
 // this lane's id, re-derived where it is needed (two VALU instructions; volatile: neither hoisted nor kept): anything derived from the
@@ -262,6 +270,113 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   const int wg_seq = (int)blockIdx.x / NSPL, chunk0 = SPLIT ? (int)blockIdx.x % NSPL : 0, gseq = (int)gridDim.x / NSPL;
   if (wg_seq >= B) return;
 
+  bf16x8 bfr[STILES][KS];      // the operand of a sequence and step: every B fragment of the wave, resident for all chunks
+  // Self-start (ONE sequence per workgroup: the host launches B workgroups, so this IS the top of every sequence and the loop below runs
+  // once -- beyond one workgroup per CU they start as CUs free up, which is the order the persistent loop walks them in): the operand [h0 | x_0] from the USER layout (h0 [B][F][N],
+  // X[b][0] [G][N]: rows = features), one 32-feature k-step at a time through the two hop-image planes, idle until the first seed: 32 rows x
+  // NP nodes x 2 B = 64 KB below BIAS_OFF, ALL pieces of a k-step in flight per wave (8 x 16 B per lane), one vmcnt(0), a barrier -- then
+  // lane (r, q) of tile i picks features 32 s + 8 q .. + 7 of its slot's node out of rows 8 q .. 8 q + 7, which IS bfr[i][s]: no global
+  // round trip. The 16-byte pieces of row R sit rotated by 2 (R >> 3) places (by the SOURCE address: an LDS-DMA destination is
+  // lane-linear), so the four quads of a wave -- rows 8 apart, 2 KB pitch = the same banks -- read bank groups 8 dwords apart. Columns
+  // >= N are not fetched and rows >= N read as zeros, exactly what the caller's pack wrote. It runs FIRST, in front of the tile tables and
+  // the launch's own LDS-DMA (which land above WOFF): here next to no scalar register is live yet -- at the top of the sequence loop every
+  // scalar this code uses was one more spill lane of a kernel that sits at 255 vector registers.
+  constexpr bool SELFV = PKV && SCRV && MODE == 0 && !GATED && !SPLIT;      // (VAR 7 and 13: the un-gated inference forward and its output-head form, uniform-weight or rank-1)
+  const bool self_start = SELFV && a.self_start != 0;      // (wave-uniform: a kernel argument)
+  if constexpr (SELFV) {
+    if (self_start) {
+      constexpr int SROW = NP * 2, SPIECES = 32 * (NP / 8);      // bytes per staged feature row, 16-byte pieces per k-step
+      static_assert(32 * SROW <= M::BIAS_OFF && 32 * SROW <= M::WOFF && SPIECES % STHREADS == 0 && NP / 8 == 128, "self-start staging area: below the bias table");
+      const int b = wg_seq;
+      const int tl = wave * 64 + lane_now();
+      int nodes[STILES];      // this lane's slot nodes (the slot table is not in LDS yet)
+#pragma unroll
+      for (int i = 0; i < STILES; ++i) nodes[i] = a.tile_nodes[(wave * STILES + i) * 16 + (tl & 15)] >> 16;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const uint16_t* src = s < HS ? a.h0u + (int64_t)b * (F * N) + (int64_t)(32 * s) * N
+                                     : a.pk_src0 + (int64_t)b * a.pk_stride + (int64_t)(32 * (s - HS)) * N;
+#pragma unroll
+        for (int i = 0; i < SPIECES / STHREADS; ++i) {
+          const int id = i * STHREADS + tl;
+          const int row = id >> 7, cs = id & 127;
+          const int col = (cs - 2 * (row >> 3)) & 127;
+          if (col * 8 < N)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (int64_t)row * N + col * 8),
+                                             (__attribute__((address_space(3))) void*)(smem + (i * STHREADS + wave * 64) * 16), 16, 0, GCRNN_SEQ32_NT_DMA);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        lds_barrier();      // every wave's pieces of the k-step are in
+        const int qo = (tl & 63) >> 4;
+#pragma unroll
+        for (int i = 0; i < STILES; ++i) {
+          const bool ok = nodes[i] < N;
+          const int nn = ok ? nodes[i] : 0;
+          const char* ra = smem + (8 * qo) * SROW + ((((nn >> 3) + 2 * qo) & 127) << 4) + (nn & 7) * 2;
+          uint32_t h16[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) h16[j] = *reinterpret_cast<const uint16_t*>(ra + j * SROW);
+          typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4s_t;
+          u32x4s_t v;
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) v[jj] = ok ? (h16[2 * jj] | (h16[2 * jj + 1] << 16)) : 0u;
+          bfr[i][s] = __builtin_bit_cast(bf16x8, v);
+        }
+        lds_barrier();      // the area is read: the next k-step's pieces may overwrite it
+      }
+      // x_1: step 0's ordinary pack rounds lay out rounds >= RPH of it (pack_target), shifted by one hop as in every step; the first RPH
+      // rounds -- nodes [0, RPH * 128), which no hop of step 0 reaches -- are laid out here, through the same area: G rows x XN nodes, rotated
+      // as above, then one 16-byte piece (node, 8 features) per lane and trip, the bytes pack_drain writes. Stored before step 0's first hop,
+      // and every hop waits (vmcnt(0) + barrier) before the step's last epilogue requests x_1.
+      if (a.nsteps > 1) {
+        constexpr int XN = RPH * NPCK, XROWS = G, XPPR = XN / 8, XPCS = XROWS / 8;
+        static_assert(XROWS * XN * 2 <= 32 * SROW && (XROWS * XPPR) % STHREADS == 0 && (XPCS * XN) % STHREADS == 0 && XPPR >= 16, "x_1 start-up rounds");
+        // (gfx950 store-data hazard, DESIGN 4.1: the stores take an immediate soffset -- the sequence is in the descriptor's base --, every piece
+        //  of a pass sits in its own register tuple before the first store, and the tuples stay reserved until the stores have retired)
+        const __amdgpu_buffer_rsrc_t rsrc_x1 = __builtin_amdgcn_make_buffer_rsrc(a.pk_dst0 + a.pkdst_stride + (int64_t)b * (NP * G), 0, NP * G * 2, 0x00020000);
+        const uint16_t* src = a.pk_src0 + (int64_t)b * a.pk_stride + a.pksrc_stride;
+#pragma unroll
+        for (int i = 0; i < XROWS * XPPR / STHREADS; ++i) {
+          const int id = i * STHREADS + tl;
+          const int row = id / XPPR, cs = id - row * XPPR;
+          const int col = (cs - 2 * (row >> 3) + XPPR) % XPPR;      // (RPH = 3 at K = 4, F = 32: no power of two)
+          if (col * 8 < N)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (int64_t)row * N + col * 8),
+                                             (__attribute__((address_space(3))) void*)(smem + (i * STHREADS + wave * 64) * 16), 16, 0, GCRNN_SEQ32_NT_DMA);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        lds_barrier();
+        constexpr int XRI = XPCS * XN / STHREADS;
+        typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4x_t;
+        u32x4x_t vv[XRI];
+#pragma unroll
+        for (int i = 0; i < XRI; ++i) {
+          const int id = i * STHREADS + tl;
+          const int nl = id / XPCS, pc = id - nl * XPCS;
+          const char* ra = smem + (8 * pc) * (XN * 2) + ((((nl >> 3) + 2 * pc) % XPPR) << 4) + (nl & 7) * 2;
+          uint32_t h16[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) h16[j] = *reinterpret_cast<const uint16_t*>(ra + j * (XN * 2));
+          const bool ok = nl < N;
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) vv[i][jj] = ok ? (h16[2 * jj] | (h16[2 * jj + 1] << 16)) : 0u;
+        }
+#pragma unroll
+        for (int i = 0; i < XRI; ++i) asm volatile("" : "+v"(vv[i]));
+#pragma unroll
+        for (int i = 0; i < XRI; ++i) {
+          const int id = i * STHREADS + tl;
+          const int nl = id / XPCS, pc = id - nl * XPCS;
+          __builtin_amdgcn_raw_buffer_store_b128(vv[i], rsrc_x1, nl * (G * 2) + pc * 16, 0, 0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < XRI; ++i) asm volatile("" ::"v"(vv[i]));      // (reserved until here)
+        lds_barrier();      // the area is read: the launch's tables and the seed may follow
+      }
+    }
+  }
+
   // once per launch: tile tables, and -- by LDS-DMA, all pieces in flight together -- the column image and chunk 0's weights
   int tbeg[STILES], tend[STILES];
 #pragma unroll
@@ -361,7 +476,6 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   const int skip_hi = __builtin_amdgcn_readfirstlane((MODE == 3 || (MODE == 1 && a.flags && a.flags[0] != 0)) ? 1 : 0);      // (MODE 3: the operand is [0 | x_t])
   const bool skip_h = skip_hi != 0;
   // ---- the operand of a sequence and step: every B fragment of the wave, resident for all chunks ----------------------------------
-  bf16x8 bfr[STILES][KS];
   // the operand of item / sequence `bb` (its first step): at the top of the loop, or -- MODE 1 -- requested behind the previous item's last state
   // stores, when the operand registers have just died (the items of the pre-pass are one step each: without it every item starts with a
   // wait for its whole operand)
@@ -385,7 +499,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       }
     }
   };
-  bool have_operand = false;      // (wave-uniform)
+  bool have_operand = self_start;      // (wave-uniform; self-start: the one sequence's operand is in the registers already)
   for (int b = wg_seq; b < B; b += gseq) {
   if (!have_operand) load_first_operand(b);
   have_operand = false;
@@ -560,7 +674,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         const int wrap = v >= NRND ? 1 : 0;
         rnd = v - wrap * NRND;
         tgt = step + 1 + wrap;
-        return pk_any && tgt >= 2 && tgt < a.nsteps;
+        return pk_any && tgt >= (self_start ? 1 : 2) && tgt < a.nsteps;      // (self-start: step 0's rounds lay out x_1 too -- rounds >= RPH of it)
       };
       // inline pack, round rnd of step tgt: x_tgt[:, rnd * 128 .. + 127] (user layout, rows = features) by LDS-DMA into the tile ...
       auto pack_issue = [&](int v) {

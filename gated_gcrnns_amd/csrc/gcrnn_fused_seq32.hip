@@ -9,11 +9,13 @@
 //   Fout output rows over F state and G input features: Fout = F for a cell, 2 F for the two time gates' sub-cells stacked (gate pair pre-pass).
 template <typename W>
 __global__ void pack_weights_wide_kernel(const W* __restrict__ wA, const W* __restrict__ wB, uint16_t* __restrict__ out,
-                                         int Fout, int F, int G, int Kin, int Kst, int K, float w) {
+                                         int Fout, int F, int G, int Kin, int Kst, int K, float w,
+                                         const W* __restrict__ bias = nullptr, float* __restrict__ bias_out = nullptr) {
   const int KS = (F + G) / 32;
   const int64_t total = (int64_t)(Fout / 32) * K * 2 * KS * 64 * 8;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
+  if (bias_out && idx < Fout) bias_out[idx] = (float)bias[idx];      // the kernels' fp32 bias table (total >= 32 Fout)
   const int j = idx & 7, lane = (idx >> 3) & 63;
   int64_t rest = idx >> 9;
   const int s = rest % KS; rest /= KS;
@@ -46,6 +48,27 @@ extern "C" int gcrnn_fused_pack_weights_wide(int wdtype, const void* wA, const v
         (const __hip_bfloat16*)wA, (const __hip_bfloat16*)wB, (uint16_t*)wpack, (int)Fout, (int)F, (int)G, (int)Kin, (int)Kst, K, (float)uniform_w);
   else
     return GCRNN_ERR_BAD_DTYPE;
+  GCRNN_CHECK_LAUNCH();
+  return GCRNN_OK;
+}
+
+// gcrnn_fused_pack_weights_wide + the fp32 copy of the cell's bias [Fout] (same dtype as the taps) in ONE launch: bias_out [Fout] fp32 is
+// what the wide forward's `bias` argument takes. Replaces a conversion launch of its own in front of every forward.
+extern "C" int gcrnn_fused_pack_weights_wide_bias(int wdtype, const void* wA, const void* wB, const void* bias, void* wpack, float* bias_out,
+                                                  int64_t Fout, int64_t F, int64_t G, int64_t Kin, int64_t Kst, double uniform_w, void* stream) {
+  if (!wA || !wB || !wpack || !bias || !bias_out) return GCRNN_ERR_NULL_POINTER;
+  if (F <= 0 || G < 0 || F % 32 || (F + G) % 32 || Fout <= 0 || Fout % 32 || Kin <= 0 || Kst <= 0 || uniform_w == 0.0) return GCRNN_ERR_BAD_SHAPE;
+  if (wdtype != GCRNN_F32 && wdtype != GCRNN_BF16) return GCRNN_ERR_BAD_DTYPE;
+  const int K = (int)(Kin > Kst ? Kin : Kst);
+  const int64_t total = (Fout / 32) * K * 2 * ((F + G) / 32) * 64 * 8;
+  GCRNN_PRE_LAUNCH();
+  if (wdtype == GCRNN_F32)
+    pack_weights_wide_kernel<float><<<(unsigned)cdiv(total, 256), 256, 0, as_stream(stream)>>>(
+        (const float*)wA, (const float*)wB, (uint16_t*)wpack, (int)Fout, (int)F, (int)G, (int)Kin, (int)Kst, K, (float)uniform_w, (const float*)bias, bias_out);
+  else
+    pack_weights_wide_kernel<__hip_bfloat16><<<(unsigned)cdiv(total, 256), 256, 0, as_stream(stream)>>>(
+        (const __hip_bfloat16*)wA, (const __hip_bfloat16*)wB, (uint16_t*)wpack, (int)Fout, (int)F, (int)G, (int)Kin, (int)Kst, K, (float)uniform_w,
+        (const __hip_bfloat16*)bias, bias_out);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -253,7 +276,7 @@ static int forward_wide_impl(const void* xs, const void* h0, void* hs, void* scr
                              const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4, int64_t entries,
                              int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, void* Huser,
                              int huser_last_only, const void* Xuser_inline, const float* rank1_a, const float* rank1_b,
-                             void* stream) {
+                             void* stream, bool self_start = false /* h0 is the USER-layout tensor, xs a work buffer (gcrnn_fused_forward_wide_user_bf16) */) {
   if (!xs || !h0 || (!no_image && !hs) || !wpack || !tile_nodes || !tile_off || !ell_col4) return GCRNN_ERR_NULL_POINTER;
   if (no_image && !Huser) return GCRNN_ERR_NULL_POINTER;
   if ((rank1_a == nullptr) != (rank1_b == nullptr)) return GCRNN_ERR_BAD_SHAPE;
@@ -262,6 +285,7 @@ static int forward_wide_impl(const void* xs, const void* h0, void* hs, void* scr
   if (B * (NP * (F > G ? F : G) * 2) > 2147483647LL || T * F * N > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;   // 32-bit buffer offsets
   if (Huser && (N % 8 != 0 || (reinterpret_cast<uintptr_t>(Huser) & 15))) return GCRNN_ERR_BAD_SHAPE;
   if (Xuser_inline && (N % 8 != 0 || (reinterpret_cast<uintptr_t>(Xuser_inline) & 15) || T * G * N > 2147483647LL)) return GCRNN_ERR_BAD_SHAPE;
+  if (self_start && (!no_image || gi || !Xuser_inline)) return GCRNN_ERR_UNSUPPORTED;
   if (no_image) {      // (checked before anything is launched)
     if (F % 32 || F < 32) return GCRNN_ERR_UNSUPPORTED;
     const int64_t need = seq32_scratch_need(B, F);
@@ -270,9 +294,13 @@ static int forward_wide_impl(const void* xs, const void* h0, void* hs, void* scr
   const int64_t xstep = B * NP * G, hstep = B * NP * F;
   Seq32Args sa{};
   sa.x0 = (const uint16_t*)xs; sa.xstride = xstep;
-  sa.hfirst = (const uint16_t*)h0;
+  sa.hfirst = self_start ? nullptr : (const uint16_t*)h0;
+  sa.h0u = self_start ? (const uint16_t*)h0 : nullptr; sa.self_start = self_start ? 1 : 0;
   sa.out0 = no_image ? nullptr : (uint16_t*)hs; sa.ostride = hstep;
   sa.scr = no_image ? (uint16_t*)scratch : nullptr;
+  // self-start launches one workgroup per sequence: past the persistent grid `scratch` (sized by that grid) has no block for the later ones.
+  // Slot 0 of the work buffer, [B][NP][G] bf16 that this form never touches, holds B blocks of (F/32 - 1) NP 64 bytes (F/32 - 1 <= 1 <= G/32).
+  if (self_start && B > gcrnn_persistent_grid()) sa.scr = const_cast<uint16_t*>((const uint16_t*)xs);
   sa.wpack = (const uint4*)wpack; sa.bias = bias;
   sa.a1 = (const uint16_t*)Huser; sa.a1stride = F * N; sa.a1_last_only = huser_last_only ? 1 : 0;
   sa.ubstride = (int)((huser_last_only ? 1 : T) * F * N);
@@ -286,7 +314,7 @@ static int forward_wide_impl(const void* xs, const void* h0, void* hs, void* scr
     const char* sg = getenv("GCRNN_SEQ32_STAGGER");
     sa.stagger = sg ? atoi(sg) : 0;
   }
-  const bool inline_pack = Xuser_inline != nullptr && T > 2;
+  const bool inline_pack = Xuser_inline != nullptr && (T > 2 || self_start);      // (self-start: the inline-pack form at every T, it reads x_0 through pk_src0)
   if (inline_pack) {      // (the kernel lays out steps 2 .. T-1, each finished one hop before the step that reads it ends: gcrnn_fused_seq32.h)
     sa.pk_src0 = (const uint16_t*)Xuser_inline; sa.pksrc_stride = G * N;
     sa.pk_dst0 = const_cast<uint16_t*>(sa.x0); sa.pkdst_stride = xstep;
@@ -331,13 +359,72 @@ extern "C" int gcrnn_fused_forward_wide_bf16(const void* xs, const void* h0, voi
                            huser_last_only, Xuser_inline, rank1_a, rank1_b, stream);
 }
 
+// Self-start (gcrnn_fused_seq32.h, Seq32Args::self_start): gcrnn_fused_forward_wide_scratch_bf16 WITHOUT the caller's layout launches -- h0
+// is the USER-layout tensor [B][F][N] bf16 (16-byte aligned), Xuser the user-layout X [B][T][G][N] (required), and the launch itself stages
+// [h0 | x_0] of each sequence through LDS and lays out x_1 during step 0. It replaces gcrnn_pack_seq_major (h0) + gcrnn_pack_seq_major_steps
+// (x_0, x_1) + gcrnn_fused_forward_wide_scratch_bf16. xs_work [T][B][NPad][G] bf16 (xs_bytes >= gcrnn_fused_forward_wide_user_bytes) is a work
+// buffer of the launch: contents undefined before and after. Un-gated cells only; every T >= 1; one workgroup per sequence. Everything is validated before the launch:
+// GCRNN_ERR_BAD_SHAPE for N % 8 != 0, a misaligned pointer or a buffer that is too small, GCRNN_ERR_UNSUPPORTED for F or G that are no
+// multiples of 32 or a problem the persistent state-scratch form does not take. gcrnn_fused_forward_wide_user_supported: 1 when it takes the
+// problem -- 0 also with GCRNN_SEQ32_SELF_START=0 (read at every call: the caller then issues the launches named above; same-binary A/B).
+// The same launch is reached through gcrnn_fused_forward_wide_scratch_bf16 with GCRNN_WIDE_SELF_START set in huser_last_only (h0 and xs then
+// mean h0_user and xs_work; there is no size to check xs against) -- the form ops.fused_cell_forward issues, so that the un-gated inference
+// forward stays ONE call of that entry point whichever way its inputs are laid out.
+static bool seq32_self_start_wanted() {
+  const char* e = getenv("GCRNN_SEQ32_SELF_START");
+  return !(e && e[0] == '0');
+}
+
+extern "C" int64_t gcrnn_fused_forward_wide_user_bytes(int64_t B, int64_t T, int64_t G) {
+  if (B <= 0 || T <= 0 || G <= 0) return -1;
+  return T * B * (int64_t)NP * G * 2;
+}
+
+extern "C" int gcrnn_fused_forward_wide_user_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries,
+                                                       double uniform_w, int img16) {
+  if (!seq32_self_start_wanted() || F < 32 || F % 32 || G < 32 || G % 32 || N % 8) return 0;
+  if (!gcrnn_fused_forward_wide_supported(B, T, N, F, G, K, entries, uniform_w, img16, 1)) return 0;
+  if (!seq32_wanted(B)) return 0;      // (a split batch: one launch per step)
+  if (B * F * N > 2147483647LL) return 0;
+  return gcrnn_fused_forward_wide_scratch_bytes(B, F, (img16 & 2) ? 1 : 0) >= 0 ? 1 : 0;
+}
+
+// (argument checks of the self-start forms that need no device: before anything else)
+static int seq32_user_args_check(const void* xs_work, int64_t xs_bytes, const void* h0_user, const void* Xuser, int64_t B, int64_t T, int64_t N,
+                                 int64_t F, int64_t G) {
+  if (!xs_work || !h0_user || !Xuser) return GCRNN_ERR_NULL_POINTER;
+  if (B <= 0 || T <= 0 || N <= 0 || N > NP || N % 8) return GCRNN_ERR_BAD_SHAPE;
+  if (F < 32 || F % 32 || G < 32 || G % 32) return GCRNN_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(h0_user) & 15) || (reinterpret_cast<uintptr_t>(xs_work) & 15) || B * F * N > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
+  if (xs_bytes < gcrnn_fused_forward_wide_user_bytes(B, T, G)) return GCRNN_ERR_BAD_SHAPE;
+  return GCRNN_OK;
+}
+
 extern "C" int gcrnn_fused_forward_wide_scratch_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack, const float* bias,
                                                      const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4,
                                                      int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, void* Huser,
                                                      int huser_last_only, const void* Xuser_inline, const float* rank1_a, const float* rank1_b,
                                                      void* stream) {
+  // (2 and 3 only: every other non-zero value keeps meaning "the last state only", as before the flag existed)
+  const bool self_start = huser_last_only == GCRNN_WIDE_SELF_START || huser_last_only == (GCRNN_WIDE_SELF_START | 1);
+  if (self_start) {
+    if (gi || gf) return GCRNN_ERR_BAD_SHAPE;
+    const int rc = seq32_user_args_check(xs, INT64_MAX, h0, Xuser_inline, B, T, N, F, G);
+    if (rc != GCRNN_OK) return rc;
+  }
   return forward_wide_impl(xs, h0, nullptr, scratch, scratch_bytes, true, wpack, bias, gi, gf, tile_nodes, tile_off, ell_col4, entries, B, T, N, F, G, K, Huser,
-                           huser_last_only, Xuser_inline, rank1_a, rank1_b, stream);
+                           self_start ? (huser_last_only & 1) : huser_last_only, Xuser_inline, rank1_a, rank1_b, stream, self_start);
+}
+
+extern "C" int gcrnn_fused_forward_wide_user_bf16(void* xs_work, int64_t xs_bytes, const void* h0_user, void* scratch, int64_t scratch_bytes,
+                                                  const void* wpack, const float* bias, const int32_t* tile_nodes, const int32_t* tile_off,
+                                                  const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K,
+                                                  void* Huser, int huser_last_only, const void* Xuser, const float* rank1_a, const float* rank1_b,
+                                                  void* stream) {
+  const int rc = seq32_user_args_check(xs_work, xs_bytes, h0_user, Xuser, B, T, N, F, G);
+  if (rc != GCRNN_OK) return rc;
+  return forward_wide_impl(xs_work, h0_user, nullptr, scratch, scratch_bytes, true, wpack, bias, nullptr, nullptr, tile_nodes, tile_off, ell_col4, entries,
+                           B, T, N, F, G, K, Huser, huser_last_only & 1, Xuser, rank1_a, rank1_b, stream, true);
 }
 
 // Inference of cell + output head Linear(F -> 1) shared by all nodes as ONE launch (gcrnn_fused_seq32.h VAR bit 3, instantiated in
@@ -358,11 +445,11 @@ extern "C" int gcrnn_fused_forward_wide_head_supported(int64_t B, int64_t T, int
   return gcrnn_seq32h_lds(F, G, K, entries, inline_pack != 0 && T > 2, (img16 & 2) != 0) ? 1 : 0;
 }
 
-extern "C" int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack, const float* bias,
-                                                  const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4,
-                                                  int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K,
-                                                  const float* head_w, const float* head_b, float* Y, const void* Xuser_inline,
-                                                  const float* rank1_a, const float* rank1_b, void* stream) {
+static int forward_wide_head_impl(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack, const float* bias,
+                                  const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4,
+                                  int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K,
+                                  const float* head_w, const float* head_b, float* Y, const void* Xuser_inline,
+                                  const float* rank1_a, const float* rank1_b, void* stream, bool self_start) {
   if (!xs || !h0 || !wpack || !tile_nodes || !tile_off || !ell_col4 || !Y || !head_w) return GCRNN_ERR_NULL_POINTER;
   if ((rank1_a == nullptr) != (rank1_b == nullptr)) return GCRNN_ERR_BAD_SHAPE;
   if ((gi == nullptr) != (gf == nullptr) || (gi && Xuser_inline)) return GCRNN_ERR_BAD_SHAPE;
@@ -378,8 +465,9 @@ extern "C" int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0
   if (!rank1_a && !seq32_wanted(B) && seq32_split_wanted(B, F)) return GCRNN_ERR_UNSUPPORTED;      // a split batch hands h_t over between launches
   Seq32Args sa{};
   sa.x0 = (const uint16_t*)xs; sa.xstride = B * NP * G;
-  sa.hfirst = (const uint16_t*)h0;
-  sa.scr = (uint16_t*)scratch;
+  sa.hfirst = self_start ? nullptr : (const uint16_t*)h0;
+  sa.h0u = self_start ? (const uint16_t*)h0 : nullptr; sa.self_start = self_start ? 1 : 0;
+  sa.scr = (self_start && B > gcrnn_persistent_grid()) ? const_cast<uint16_t*>((const uint16_t*)xs) : (uint16_t*)scratch;      // (as in forward_wide_impl)
   sa.wpack = (const uint4*)wpack; sa.bias = bias;
   sa.head_w = head_w; sa.head_b = head_b; sa.y0 = Y;
   sa.tile_nodes = tile_nodes; sa.tile_off = tile_off; sa.ell_col4 = (const uint2*)ell_col4;
@@ -391,13 +479,42 @@ extern "C" int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0
     const char* sg = getenv("GCRNN_SEQ32_STAGGER");
     sa.stagger = sg ? atoi(sg) : 0;
   }
-  const bool inline_pack = Xuser_inline != nullptr && T > 2;
+  const bool inline_pack = Xuser_inline != nullptr && (T > 2 || self_start);
   if (inline_pack) {      // (the kernel lays out steps 2 .. T-1: gcrnn_fused_seq32.h)
     sa.pk_src0 = (const uint16_t*)Xuser_inline; sa.pksrc_stride = G * N;
     sa.pk_dst0 = const_cast<uint16_t*>(sa.x0); sa.pkdst_stride = sa.xstride;
     sa.pk_stride = (int)(T * G * N);
   }
   return gcrnn_seq32h_forward(sa, (int)K, (int)(F / 32), (int)(G / 32), inline_pack, as_stream(stream));
+}
+
+extern "C" int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0, void* scratch, int64_t scratch_bytes, const void* wpack, const float* bias,
+                                                  const float* gi, const float* gf, const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4,
+                                                  int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K,
+                                                  const float* head_w, const float* head_b, float* Y, const void* Xuser_inline,
+                                                  const float* rank1_a, const float* rank1_b, void* stream) {
+  return forward_wide_head_impl(xs, h0, scratch, scratch_bytes, wpack, bias, gi, gf, tile_nodes, tile_off, ell_col4, entries, B, T, N, F, G, K, head_w, head_b, Y,
+                                Xuser_inline, rank1_a, rank1_b, stream, false);
+}
+
+// The head variant's self-start form (VAR 13): gcrnn_fused_forward_wide_user_bf16's arguments with Huser / huser_last_only replaced by head_w,
+// head_b and Y as in gcrnn_fused_forward_wide_head_bf16 -- which, with the caller's two layout launches, it replaces; same checks and codes.
+extern "C" int gcrnn_fused_forward_wide_head_user_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries,
+                                                            double uniform_w, int img16) {
+  if (!gcrnn_fused_forward_wide_user_supported(B, T, N, F, G, K, entries, uniform_w, img16)) return 0;
+  if (B * T * N > 2147483647LL) return 0;
+  return gcrnn_seq32h_lds(F, G, K, entries, true, (img16 & 2) != 0) ? 1 : 0;
+}
+
+extern "C" int gcrnn_fused_forward_wide_head_user_bf16(void* xs_work, int64_t xs_bytes, const void* h0_user, void* scratch, int64_t scratch_bytes,
+                                                       const void* wpack, const float* bias, const int32_t* tile_nodes, const int32_t* tile_off,
+                                                       const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G,
+                                                       int64_t K, const float* head_w, const float* head_b, float* Y, const void* Xuser,
+                                                       const float* rank1_a, const float* rank1_b, void* stream) {
+  const int rc = seq32_user_args_check(xs_work, xs_bytes, h0_user, Xuser, B, T, N, F, G);
+  if (rc != GCRNN_OK) return rc;
+  return forward_wide_head_impl(xs_work, h0_user, scratch, scratch_bytes, wpack, bias, nullptr, nullptr, tile_nodes, tile_off, ell_col4, entries, B, T, N, F, G, K,
+                                head_w, head_b, Y, Xuser, rank1_a, rank1_b, stream, true);
 }
 
 

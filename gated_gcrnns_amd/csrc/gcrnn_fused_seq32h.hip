@@ -12,7 +12,9 @@ static int seq32h_launch_v(const Seq32Args& sa, size_t lds, hipStream_t st) {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(sk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
-  sk<<<(unsigned)(sa.B < gcrnn_persistent_grid() ? sa.B : gcrnn_persistent_grid()), STHREADS, lds, st>>>(sa);      // one workgroup per CU: the scratch is sized by this grid
+  // one workgroup per CU: the scratch is sized by this grid. Self-start: one workgroup per SEQUENCE (its start-up phase runs in front of the
+  // kernel's tables) -- beyond the persistent grid they start as CUs free up, and the entry point has put their scratch into the work buffer
+  sk<<<(unsigned)((sa.B < gcrnn_persistent_grid() || sa.self_start) ? sa.B : gcrnn_persistent_grid()), STHREADS, lds, st>>>(sa);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }

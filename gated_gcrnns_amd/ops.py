@@ -388,9 +388,14 @@ def time_fused_step_kernel(X, h0, wA, wB, bias, graph, reps=3, inline=None, user
         # the wide sequence-resident kernel (what fused_cell_forward issues for this problem): ONE launch per forward
         wpw = _fused_pack_weights_wide(wAc, wBc, wide['uniform_w'], st)
         scr = fused_state_scratch(wide, B, F, dev) if H is not None else None      # the launch the module issues under no_grad: no state image
+        # ... and with the inline pack the self-start form, which reads the user-layout X and h0 itself (fused_cell_forward's dispatch)
+        user16 = fused_wide_user_plan(graph, Xc, h0c, F, G, K) if (H is not None and scr is not None and inline) else None
         for rep in range(reps + warm):
             if rep == warm:
                 e0.record()                              # (no synchronisation here: the timed launches follow the warm ones without an idle gap)
+            if user16 is not None:
+                _fused_forward_wide_user(user16, Xc, h0c, wAc, wBc, None, F, G, K, st, out=H, packs=(wpw, b32), buffers=(xs.view(torch.uint8).view(-1), scr))
+                continue
             _fused_forward_wide(wide, xs, h0s, hs, wAc, wBc, b32, B, T, N, F, G, K, H, False, Xc if inline else None, st, wpw=wpw, scratch=scr)
         e1.record()
         torch.cuda.synchronize()
@@ -519,6 +524,86 @@ def _fused_pack_weights_wide(wA, wB, uniform_w, st):
     return _cached_pack('taps32', (wA.detach(), wB.detach()), float(uniform_w), st, make)
 
 
+def _fused_pack_weights_wide_bias(wA, wB, bias, uniform_w, st):
+    """_fused_pack_weights_wide of a cell's taps together with the fp32 copy of its bias [F], written by the SAME launch
+    (gcrnn_fused_pack_weights_wide_bias): (wpack, b32). Kept under the live-parameter rule of _cached_pack like the two it replaces. A bias
+    of another dtype than the taps (or none) takes the two separate packs."""
+    if bias is None or bias.dtype != wB.dtype or wA.dtype != wB.dtype:
+        return _fused_pack_weights_wide(wA, wB, uniform_w, st), _bias_f32(bias, st)
+    Fout, G, F = wA.shape[0], wA.shape[3], wB.shape[3]
+    Kin, Kst = wA.shape[2], wB.shape[2]
+    K = max(Kin, Kst)
+    b = bias.detach()
+    assert b.numel() == Fout and G > 0
+
+    def make():
+        wpack = torch.empty(((Fout // 32) * K * 2 * ((F + G) // 32) * 64 * 8,), dtype=torch.bfloat16, device=wA.device)
+        b32 = torch.empty((Fout,), dtype=torch.float32, device=wA.device)
+        wAc, wBc, bc = wA.contiguous(), wB.contiguous(), b.contiguous()
+        check(lib.gcrnn_fused_pack_weights_wide_bias(dtype_code(wB.dtype), _p(wAc), _p(wBc), _p(bc), _p(wpack), _p(b32), Fout, F, G, Kin, Kst,
+                                                     float(uniform_w), st), 'pack_weights_wide_bias')
+        return wpack, b32
+    return _cached_pack('taps32b', (wA.detach(), wB.detach(), b), float(uniform_w), st, make)
+
+
+def fused_wide_user_plan(graph, X, h0, F, G, K, head=False):
+    """The bf16-image plan (uniform-weight or rank-1) when the SELF-START form of the wide inference forward takes the problem (the launch
+    reads the user-layout h0 and X itself: no layout launch in front of it; csrc/gcrnn_fused_seq32.h), else None. X [B][T][G][N],
+    h0 [B][F][N]: contiguous bf16, 16-byte aligned, N % 8 == 0, F and G multiples of 32; every T >= 1 (T <= 2 included: the form needs
+    no caller-packed x_1) and every B (one workgroup per sequence). head: the output-head launch's form. GCRNN_SEQ32_SELF_START=0 (read by the library at every call) and GCRNN_NO_INLINE_PACK=1 switch it off."""
+    B, T, _, N = X.shape
+    if (os.environ.get('GCRNN_NO_INLINE_PACK') or X.dtype != torch.bfloat16 or h0.dtype != torch.bfloat16 or X.shape[2] != G
+            or not X.is_contiguous() or not h0.is_contiguous() or X.data_ptr() % 16 or h0.data_ptr() % 16 or N % 8 or F % 32 or G % 32):
+        return None
+    plan16 = _forward_plan16(graph)
+    if plan16 is None:
+        plan16 = _forward_plan16(graph, rank1=True)
+    if plan16 is None:
+        return None
+    query = lib.gcrnn_fused_forward_wide_head_user_supported if head else lib.gcrnn_fused_forward_wide_user_supported
+    ok = query(int(B), int(T), int(N), int(F), int(G), int(K), int(plan16['entries']), float(plan16.get('uniform_w', 0.0)),
+               3 if plan16.get('rank1') else 1)
+    return plan16 if ok else None
+
+
+_WIDE_SELF_START = 2      # GCRNN_WIDE_SELF_START (include/gcrnn.h): bit 1 of gcrnn_fused_forward_wide_scratch_bf16's huser_last_only
+
+
+def _fused_forward_wide_user(plan16, X, h0, wA, wB, bias, F, G, K, st, last_only=False, out=None, packs=None, buffers=None, head=None):
+    """ONE weight + bias pack launch and ONE launch of the wide kernel's self-start form on the user-layout X and h0 -- issued through
+    gcrnn_fused_forward_wide_scratch_bf16 with GCRNN_WIDE_SELF_START (the un-gated inference forward is one call of that entry point
+    whichever way its inputs are laid out; gcrnn_fused_forward_wide_user_bf16 is the same launch for C callers). Returns H [B][T or 1][F][N]
+    bf16 -- or, head = (hw [F] fp32, hb [1] fp32 or None), y [B][T][N] fp32 from gcrnn_fused_forward_wide_head_user_bf16. The work buffer and the scratch are allocated per call on the current stream (two forwards on two streams never share them)
+    unless the caller brings its own (buffers = (work, scratch))."""
+    B, T, _, N = X.shape
+    dev = X.device
+    if buffers is not None:
+        work, scr = buffers
+    else:
+        scr = fused_state_scratch(plan16, B, F, dev)
+        work = torch.empty((int(lib.gcrnn_fused_forward_wide_user_bytes(int(B), int(T), int(G))),), dtype=torch.uint8, device=dev)
+    assert scr is not None
+    wpw, b32 = packs if packs is not None else _fused_pack_weights_wide_bias(wA.detach(), wB.detach(), bias, plan16['uniform_w'], st)
+    if head is not None:
+        hw, hb = head
+        if out is None:
+            out = torch.empty((B, T, N), dtype=torch.float32, device=dev)
+        else:
+            assert out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == (B, T, N) and out.is_contiguous(), 'out: contiguous fp32 [B][T][N]'
+        check(lib.gcrnn_fused_forward_wide_head_user_bf16(_p(work), int(work.numel()), _p(h0), _p(scr), int(scr.numel()), _p(wpw), _p(b32),
+                                                          *_wide_graph_args(plan16), B, T, N, F, G, K, _p(hw), _p(hb), _p(out), _p(X),
+                                                          _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
+              'fused_forward_wide_head_user')
+        return out
+    H = out if out is not None else torch.empty((B, 1 if last_only else T, F, N), dtype=torch.bfloat16, device=dev)
+    check(lib.gcrnn_fused_forward_wide_scratch_bf16(_p(work), _p(h0), _p(scr), int(scr.numel()), _p(wpw), _p(b32), None, None,
+                                                    *_wide_graph_args(plan16), B, T, N, F, G, K, _p(H),
+                                                    int(bool(last_only)) | _WIDE_SELF_START, _p(X),
+                                                    _p(plan16.get('rank1_a')), _p(plan16.get('rank1_b')), st),
+          'fused_forward_wide_scratch (self-start)')
+    return H
+
+
 def fused_wide_plan(graph, B, T, N, F, G, K, inline, rank1=False, gated=False):
     """The bf16-image plan when the wide sequence-resident kernel (gcrnn_fused_forward_wide_bf16: un-gated forward as ONE launch, 32-feature
     chunks) takes this problem, else None. GCRNN_SEQ32=0 switches it off (A/B)."""
@@ -603,10 +688,16 @@ def _fused_forward_wide_head(plan16, xs, h0s, wA, wB, b32, B, T, N, F, G, K, hw,
     return out
 
 
-def fused_cell_forward_wide_head(X, h0, wA, wB, bias, graph, head, gates=None, gate_values=None, out=None):
+def fused_cell_forward_wide_head(X, h0, wA, wB, bias, graph, head, gates=None, gate_values=None, out=None, self_start=False):
     """Inference of cell + output head as ONE launch of the wide kernel (fused_cell_forward's arguments; head = (weight 1 x F, bias [1] or
     None)): y B x T x 1 x N fp32, a view of the [B][T][N] array the kernel writes -- `out`, when given (contiguous fp32 [B][T][N]). Raises where
     fused_wide_head_supported says no; GCRNN_NO_WIDE_HEAD does not apply here (it switches the DISPATCH of fused_cell_forward off)."""
+    if self_start:
+        # the launch reads the user-layout X and h0 itself (gcrnn_fused_forward_wide_head_user_bf16): no layout launch in front of it. Opt-in:
+        # the dispatch of fused_cell_forward(head=...) -- the regression model's forward -- is pinned by its launch-count tests to ONE call
+        # of gcrnn_fused_forward_wide_head_bf16, whose argument list has no room for the switch. Bit-identical y.
+        assert gates is None and gate_values is None, 'self_start: the un-gated cell'
+        return fused_cell_forward(X, h0, wA, wB, bias, graph, head=head, _head_out=out, _head_wide='self_start')
     return fused_cell_forward(X, h0, wA, wB, bias, graph, gates=gates, gate_values=gate_values, head=head, _head_out=out, _head_wide='require')
 
 
@@ -955,6 +1046,7 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     user-layout copy of every h_t (a third of the bytes they write); callers that need contiguity call .contiguous() themselves.
     """
     require_device(X, h0, wA, wB, bias)
+    G0 = X.shape[2]                                      # (before any channel padding)
     if packed is None and X.shape[2] < wA.shape[3]:
         # taps already padded to the kernels' input width, X still with its own G channels (the drivers' G = 1): lay X out for the
         # kernels with the channel padding done by the pack itself -- no 32-channel copy of X in the user layout
@@ -979,8 +1071,23 @@ def fused_cell_forward(X, h0, wA, wB, bias, graph, gates=None, return_states=Fal
     inline = False
     # inference through the user-layout H: the wide kernel then runs without a state image (fused_state_scratch) and hs is not allocated
     # here; a path that does need it allocates it below
-    head_wide = head is not None and (_head_wide == 'require' or not os.environ.get('GCRNN_NO_WIDE_HEAD'))      # (the wide kernel's head variant may run)
+    head_wide = head is not None and (_head_wide in ('require', 'self_start') or not os.environ.get('GCRNN_NO_WIDE_HEAD'))      # (the wide kernel's head variant may run)
     lean = packed is None and (head is None or head_wide) and not return_states and not native_out and N % 8 == 0
+    if _head_wide == 'self_start':
+        assert head is not None and lean and G0 == G and not last_only
+        user16 = fused_wide_user_plan(graph, X, h0, F, G, K, head=True)
+        if user16 is None:
+            raise RuntimeError('fused_cell_forward_wide_head(self_start=True): the self-start head form does not take this problem')
+        hw = head[0].detach().float().reshape(-1).contiguous()
+        assert hw.numel() == F
+        hb = head[1].detach().float().reshape(-1).contiguous() if head[1] is not None else None
+        return _fused_forward_wide_user(user16, X, h0, wA, wB, bias, F, G, K, st, out=_head_out, head=(hw, hb)).unsqueeze(2)      # B x T x 1 x N (a view)
+    if lean and head is None and gates is None and gate_values is None and G0 == G:
+        # the wide kernel's self-start form: the launch reads the user-layout h0 and X itself -- no layout launch, no hs_all slot 0
+        # (G < 32 keeps the channel-padding pack below; the output head's form is opt-in, fused_cell_forward_wide_head(self_start=True); GCRNN_SEQ32_SELF_START=0: the launches below, same binary)
+        user16 = fused_wide_user_plan(graph, X, h0, F, G, K)
+        if user16 is not None:
+            return _fused_forward_wide_user(user16, X, h0, wA, wB, bias, F, G, K, st, last_only=last_only)
     if packed is not None:
         xs, hs_all = packed
     elif gates is None and gate_values is None and X.data_ptr() % 16 == 0 and (

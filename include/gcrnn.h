@@ -482,6 +482,45 @@ int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0, void* scr
                                        const int32_t* tile_off, const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N,
                                        int64_t F, int64_t G, int64_t K, const float* head_w, const float* head_b, float* Y,
                                        const void* Xuser_inline, const float* rank1_a, const float* rank1_b, void* stream);
+/* Self-start form of gcrnn_fused_forward_wide_scratch_bf16: the launch lays out its own inputs. h0_user is the USER-layout state [B][F][N] bf16
+ * and Xuser the user-layout X [B][T][G][N] bf16 (both 16-byte aligned, N % 8 == 0, F and G multiples of 32, un-gated cells, every T >= 1,
+ * every B: the form launches one workgroup per sequence, whose start-up phase runs in front of the kernel's tables):
+ * each workgroup stages [h0 | x_0] of its sequence through LDS and lays out x_1 during step 0, x_2 .. as the inline pack always did.
+ * gcrnn_fused_forward_wide_user_bf16 replaces gcrnn_pack_seq_major (h0) + gcrnn_pack_seq_major_steps (x_0, x_1) +
+ *   gcrnn_fused_forward_wide_scratch_bf16; H is bit-identical to theirs. xs_work (xs_bytes >= gcrnn_fused_forward_wide_user_bytes(B, T, G) = the bytes of [T][B][NPad][G] bf16)
+ *   is a work buffer of the launch: contents undefined before and after, not to be shared by launches that may run at once.
+ *   Everything is checked before the launch: GCRNN_ERR_NULL_POINTER; GCRNN_ERR_BAD_SHAPE for N % 8 != 0, a misaligned pointer, xs_bytes or
+ *   scratch_bytes too small; GCRNN_ERR_UNSUPPORTED for F or G that are no multiples of 32 and for problems the state-scratch form does not take.
+ * gcrnn_fused_forward_wide_user_supported: 1 when the form takes the problem; 0 also with GCRNN_SEQ32_SELF_START=0 in the environment (read
+ *   at every call: the caller then issues the launches named above -- same-binary A/B).
+ * gcrnn_fused_forward_wide_head_user_bf16 / _head_user_supported: the same for the output-head launch -- Huser / huser_last_only replaced by
+ *   head_w, head_b, Y as in gcrnn_fused_forward_wide_head_bf16, which (with the two layout launches) it replaces; Y is bit-identical.
+ * `scratch`: as in the forms they replace (gcrnn_fused_forward_wide_scratch_bytes). Beyond one sequence per CU the later workgroups keep their
+ *   state in slot 0 of xs_work, which these forms never lay out.
+ * gcrnn_fused_forward_wide_user_bf16 is the documented route. The values 2 and 3 (GCRNN_WIDE_SELF_START, | 1 = "last state only") of
+ *   `huser_last_only` of gcrnn_fused_forward_wide_scratch_bf16 reach the same launch through that entry point -- its `h0` is then h0_user and
+ *   its `xs` the work buffer, with no size to check it against -- for callers that are bound to that symbol (the Python dispatch is: its
+ *   launch-count tests pin it). Every other non-zero value keeps meaning "last state only", as before.
+ * gcrnn_fused_pack_weights_wide_bias: gcrnn_fused_pack_weights_wide that also writes bias_out [Fout] fp32 = the cell's bias [Fout] (dtype of
+ *   the taps) in the same launch -- the `bias` argument of the wide forwards, without a conversion launch of its own. */
+#define GCRNN_WIDE_SELF_START 2
+int gcrnn_fused_pack_weights_wide_bias(int wdtype, const void* wA, const void* wB, const void* bias, void* wpack, float* bias_out, int64_t Fout,
+                                       int64_t F, int64_t G, int64_t Kin, int64_t Kst, double uniform_w, void* stream);
+int64_t gcrnn_fused_forward_wide_user_bytes(int64_t B, int64_t T, int64_t G);
+int gcrnn_fused_forward_wide_user_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries, double uniform_w,
+                                            int img16);
+int gcrnn_fused_forward_wide_user_bf16(void* xs_work, int64_t xs_bytes, const void* h0_user, void* scratch, int64_t scratch_bytes,
+                                       const void* wpack, const float* bias, const int32_t* tile_nodes, const int32_t* tile_off,
+                                       const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K,
+                                       void* Huser, int huser_last_only, const void* Xuser, const float* rank1_a, const float* rank1_b,
+                                       void* stream);
+int gcrnn_fused_forward_wide_head_user_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries,
+                                                 double uniform_w, int img16);
+int gcrnn_fused_forward_wide_head_user_bf16(void* xs_work, int64_t xs_bytes, const void* h0_user, void* scratch, int64_t scratch_bytes,
+                                            const void* wpack, const float* bias, const int32_t* tile_nodes, const int32_t* tile_off,
+                                            const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N, int64_t F, int64_t G,
+                                            int64_t K, const float* head_w, const float* head_b, float* Y, const void* Xuser,
+                                            const float* rank1_a, const float* rank1_b, void* stream);
 int gcrnn_fused_gate_pair_wide_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t G, int64_t K, int64_t entries, double uniform_w,
                                          int img16, int with_pack);
 /* The BPTT data chain as ONE launch of the wide kernel: gcrnn_fused_backward_data_bf16's contract (seed included), with wpackT =
