@@ -194,6 +194,13 @@ class GatedGCRNNforRegression(_GatedGCRNNBase):
             y = self.stateGCRNN.forward_with_head(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)
             if y is not None:
                 return y.to(x.dtype)
+        if self.mlpType == 'multipMlp' and torch.is_grad_enabled() and len(self.outputNN) == 1 and \
+                isinstance(self.outputNN[0], nn.Linear) and self.outputNN[0].out_features == 1:
+            # training with the drivers' head: cell + head as one autograd node whose backward hands the head's gradient to the BPTT
+            # chain as (w, dy) -- dH is never materialised; same values and gradients as the two modules below
+            y = self.stateGCRNN.train_with_head(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)
+            if y is not None:
+                return y
         H = self.stateGCRNN(x, h0)                                  # B x T x F_h x N
         flatH = H.reshape(-1, self.F_h, self.N)
         if self.mlpType == 'multipMlp':

@@ -906,6 +906,28 @@ class GGCRNNCell(nn.Module):
             return None
         return self._forward_fused(X, h0, head=(weight, bias))
 
+    def train_with_head(self, X, h0, weight, bias):
+        """Training counterpart of forward_with_head: cell + output head Linear(F -> 1) shared by all nodes as ONE autograd node
+        (ops.fused_cell_head_train). Forward: the cell's training forward and the head's kernel on H, as the two modules run them. Backward:
+        the head's gradient reaches the wide BPTT chain as its factors (w_head, dy) -- dH [B][T][F][N] and its sequence-major copy are never
+        allocated, written or read (gcrnn_fused_backward_data_wide_head_bf16) -- and every gradient equals the two-module path's bit for bit.
+        Returns y: B x T x 1 x N (bf16), or None when this cell / input does not run on that path: it needs the fused training path
+        (_use_fused_training) of the un-gated or time-gated cell, the head's bf16 kernels, a uniform-weight graph and a batch the persistent
+        wide chain takes (ops.fused_cell_head_train_supported). GCRNN_NO_HEAD_CHAIN=1 (read at every call) switches it off: A/B against the
+        two-module path."""
+        if os.environ.get('GCRNN_NO_HEAD_CHAIN') or self.spatial_gating is not None or self.F % 32 != 0 or not self._use_fused_training(X, h0):
+            return None
+        if tuple(weight.shape) != (1, self.F) or (bias is not None and bias.dtype != weight.dtype):
+            return None
+        B, T, F_in, N = X.shape
+        assert F_in == self.G and N == self.N and h0.shape[0] == B
+        if not ops.fused_cell_head_train_supported(self.graph, B, T, N, self.F, max(self.Kin, self.Kst), weight.dtype):
+            return None
+        Xp, wA = ops.fused_pad_operands(X, self.weight_A)          # G < 32 (the drivers' G = 1): zero-padded channels
+        tgates = self._fused_gates() if self.time_gating == True else None  # noqa: E712
+        y = ops.fused_cell_head_train(Xp, h0, wA, self.weight_B, self.bias, self.graph, weight, bias, tgates)
+        return y.view(B, T, 1, N)
+
     def extra_repr(self):
         return 'in_features=%d, state_features=%d, taps=(%d,%d), time_gating=%s, spatial_gating=%s, %s' % (
             self.G, self.F, self.Kin, self.Kst, self.time_gating, self.spatial_gating,

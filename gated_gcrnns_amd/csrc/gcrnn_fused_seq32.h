@@ -153,6 +153,10 @@ struct Seq32Args {
   // [h0 | x_0] of a sequence comes from the USER-layout tensors h0u [B][F][N] and pk_src0 (X[b][0]); step 0 lays out x_1. x0 / pk_dst0 is
   // then a work buffer of this launch (slot 0 is never touched), hfirst is not read.
   const uint16_t* h0u; int self_start;
+  // VAR bit 4 (MODE 2, rank-1 upstream: the loss reaches the states through an output head Linear(F -> 1) shared by all nodes, so
+  // dH_t[f][n] = head_w[f] dy_t[n] is never materialised): dy0 = dy[0][t] of chain step 0 in the USER layout [B][T][N] bf16, elements between
+  // steps (negative: backwards in time) and between sequences; head_w [F] fp32 as above. dh0_ and the pack arguments are unused.
+  const uint16_t* dy0; int64_t dystride; int64_t dybstride;
 };
 
 // this lane's id, re-derived where it is needed (two VALU instructions; volatile: neither hoisted nor kept): anything derived from the
@@ -225,6 +229,10 @@ struct Seq32Map {
 // packed registers it holds anyway -- eight FMAs per lane and tile in feature order, the four quads of a node by two xor-shuffles (16, 32),
 // the chunks in ascending order through one LDS word per slot that the same lane writes and reads (a lane keeps its slots in every chunk:
 // slot = (wave * STILES + tile) * 16 + r) -- and the q == 0 lanes store the 4-byte results straight to y [B][T][N] (rows >= N never).
+// Bit 4 (MODE 2 only, persistent form, uniform-weight graph; alone): rank-1 upstream gradient. The epilogue's operand dH_{t-1} of lane (node,
+// 8 features) is head_w[f] * dy_{t-1}[node] rounded to bf16 -- the bits the head's backward kernel would have stored into dH -- made from ONE
+// 16-bit load of dy in the user layout [B][T][N] (descriptor of the row: nodes >= N read 0) and the head's weights in the bias table's
+// place in LDS (the chain has no bias). No sequence-major dH, no pack rounds; the requests sit where the dH requests sat.
 // MODE 0: the recurrence (GATED: with the scalar time gates gi_t, gf_t known before step 0 -- they read (x_t, h0), never h_{t-1}).
 // MODE 1: the time gates' pre-pass for BOTH gates at once: an item (t, b) is one "sequence" of one step whose cell has 2 F outputs -- chunks
 //         0 .. F/32-1 the input gate's sub-cell, the rest the forget gate's (weights and biases concatenated by the caller) -- so the operand
@@ -247,6 +255,8 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   constexpr bool PKV = (VAR & 1) != 0, USERV = (VAR & 2) != 0 && (MODE == 0 || MODE == 4);
   constexpr bool SCRV = (VAR & 4) != 0;      // state scratch in slot order, no state image
   constexpr bool HEADV = (VAR & 8) != 0;     // output head in the epilogue, y instead of H
+  constexpr bool UPR1 = (VAR & 16) != 0;     // chain: the upstream gradient is head_w (x) dy, made in the epilogue
+  static_assert(!UPR1 || (VAR == 16 && MODE == 2 && !R1 && !SPLIT), "rank-1 upstream: the persistent chain on uniform-weight graphs, no inline pack");
   static_assert(!SCRV || (MODE == 0 && !SPLIT && ((VAR & 2) != 0 || HEADV)), "state scratch: the persistent forward with the user-layout output");
   static_assert(!HEADV || (SCRV && (VAR & 2) == 0), "output head: on the state scratch, no user-layout output");
   constexpr int SCR_CH = NP * 64;            // bytes of one chunk's scratch rows [NP slots][32] bf16
@@ -450,6 +460,9 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   // zeros behind the column image: the stream's running column pointer is not clamped (GCRNN_HOP_COLUMN_PAD)
   if (tid < GCRNN_HOP_COLUMN_PAD / 4) reinterpret_cast<uint32_t*>(smem + COL_OFF + entries * 32)[tid] = 0u;
   float* lbias = reinterpret_cast<float*>(smem + M::BIAS_OFF);
+  if constexpr (UPR1) {      // (the chain adds no bias: the table holds the head's weights)
+    if (tid < F) lbias[tid] = a.head_w[tid];
+  } else
   if (tid < NCH * 32) lbias[tid] = a.bias ? a.bias[tid] : 0.f;
   if constexpr (HEADV) {
     float* ht = reinterpret_cast<float*>(smem + COL_OFF + entries * 32 + GCRNN_HOP_COLUMN_PAD + NP * 4 + (R1 ? 2 * NP * 4 : 0));
@@ -510,6 +523,8 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
     [[maybe_unused]] const uint16_t* ep_dh = (SONLY && !fin && a.dh0_) ? a.dh0_ + (int64_t)step * a.dhstride : nullptr;      // (MODE 4: Yx_t)
     [[maybe_unused]] const float* ep_ng = (MODE == 4) ? a.ng0 + (int64_t)step * a.ngstride : nullptr;
     [[maybe_unused]] const uint16_t* ep_h = (MODE == 2) ? (fin ? a.final_h : (a.hs0 ? a.hs0 + (int64_t)step * a.hsstride : nullptr)) : nullptr;
+    [[maybe_unused]] const uint16_t* ep_dy = (UPR1 && !fin && a.dy0) ? a.dy0 + (int64_t)step * a.dystride + (int64_t)b * a.dybstride : nullptr;      // dy[b][t-1][:]
+    [[maybe_unused]] const bool ep_up = UPR1 ? ep_dy != nullptr : ep_dh != nullptr;      // (MODE 2: this step has an upstream term)
     [[maybe_unused]] float* gpart = (MODE == 2 && a.gpart0) ? a.gpart0 + (int64_t)step * a.gpartstride : nullptr;
     [[maybe_unused]] float gsc = 1.f;
     if constexpr (MODE == 2) {
@@ -777,7 +792,8 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       // of the tap's weight reads a few hundred cycles later and sat out the whole HBM latency: hop 1 took ~200 units instead of ~75
       // (profiles/r04_seq32_stamps_chain.txt).
       typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4e_t;
-      [[maybe_unused]] u32x4e_t eph[MODE == 2 ? STILES : 1], epg[SONLY ? STILES : 1];
+      [[maybe_unused]] u32x4e_t eph[MODE == 2 ? STILES : 1], epg[(SONLY && !UPR1) ? STILES : 1];
+      [[maybe_unused]] uint32_t epy[UPR1 ? STILES : 1];      // UPR1: dy_{t-1} of this lane's node per tile (bf16 bits)
       [[maybe_unused]] float epn[MODE == 4 ? STILES : 1][2];      // MODE 4: this lane's node's input / forget gate per tile
 #ifndef GCRNN_SEQ32_EP_FIRST
 #define GCRNN_SEQ32_EP_FIRST 1      // the requests in front of the hop's write-back (0: behind it; same-box A/B: profiles/r04_seq32_chain_requests_ab.txt)
@@ -809,12 +825,15 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           int swp[STILES];
           slot_words(lq, swp);
           const __amdgpu_buffer_rsrc_t rsrc_eh = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ep_h), 0, ep_h ? B * (NP * F * 2) : 0, 0x00020000);
-          const __amdgpu_buffer_rsrc_t rsrc_eg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ep_dh), 0, ep_dh ? B * (NP * F * 2) : 0, 0x00020000);
+          // (UPR1: the row dy[b][t-1][0 .. N) alone -- padding slots carry nodes >= N, out of range: they read 0)
+          const __amdgpu_buffer_rsrc_t rsrc_eg = UPR1 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ep_dy), 0, ep_dy ? N * 2 : 0, 0x00020000)
+                                                      : __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ep_dh), 0, ep_dh ? B * (NP * F * 2) : 0, 0x00020000);
 #pragma unroll
           for (int i = I0; i < I1; ++i) {
             const int eoff = (swp[i] >> 16) * (F * 2) + (chunk * 32 + (lq >> 4) * 8) * 2;
             eph[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_eh, eoff, b * (NP * F * 2), 0);
-            epg[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_eg, eoff, b * (NP * F * 2), 0);
+            if constexpr (UPR1) epy[i] = __builtin_amdgcn_raw_buffer_load_b16(rsrc_eg, (swp[i] >> 16) * 2, 0, 0);
+            else epg[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_eg, eoff, b * (NP * F * 2), 0);
           }
         }
       };
@@ -1074,6 +1093,11 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         // through); add the upstream gradient and go through tanh': dpre_{t-1} = (gsc acc + dH_{t-1}) (1 - h_{t-1}^2); without dH the raw state
         // gradient is stored (d h0). gpart: <h_{t-1}, acc> = <B(S) h_{t-1}, dpre_t> by the adjoint identity (the forget gate's gradient).
         float part = 0.f;
+        [[maybe_unused]] float hw8[8];      // UPR1: the head's weights of this lane's eight features (for the epilogue only)
+        if constexpr (UPR1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) hw8[e] = lbias[chunk * 32 + q * 8 + e];
+        }
 #pragma unroll
         for (int i = 0; i < STILES; ++i) {
           const int node = swe[i] >> 16;
@@ -1081,8 +1105,13 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             hv[2 * e] = bf2f((uint16_t)(eph[i][e] & 0xffffu)); hv[2 * e + 1] = bf2f((uint16_t)(eph[i][e] >> 16));
-            gv[2 * e] = bf2f((uint16_t)(epg[i][e] & 0xffffu)); gv[2 * e + 1] = bf2f((uint16_t)(epg[i][e] >> 16));
+            if constexpr (!UPR1) { gv[2 * e] = bf2f((uint16_t)(epg[i][e] & 0xffffu)); gv[2 * e + 1] = bf2f((uint16_t)(epg[i][e] >> 16)); }
             rw[e] = acc[i][0][e]; rw[4 + e] = acc[i][1][e];
+          }
+          if constexpr (UPR1) {      // dH = bf16(w dy), the fp32 product rounded to nearest-even: what the head's backward kernel stores
+            const float dyv = bf2f((uint16_t)epy[i]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) gv[e] = bf2f(f2bf(hw8[e] * dyv));
           }
           if (gpart) {
 #pragma unroll
@@ -1092,7 +1121,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             o[e] = rw[e] * gsc;
-            if (ep_dh) o[e] = (o[e] + gv[e]) * (1.f - hv[e] * hv[e]);
+            if (ep_up) o[e] = (o[e] + gv[e]) * (1.f - hv[e] * hv[e]);
           }
           u32x4_t p{0u, 0u, 0u, 0u};
           if (node < N) { p[0] = pack2bf(o[0], o[1]); p[1] = pack2bf(o[2], o[3]); p[2] = pack2bf(o[4], o[5]); p[3] = pack2bf(o[6], o[7]); }

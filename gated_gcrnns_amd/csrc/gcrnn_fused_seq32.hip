@@ -728,3 +728,56 @@ extern "C" int gcrnn_fused_backward_data_wide_bf16(const void* dHs, const void* 
 #undef GCRNN_SEQ32_CASE
   return GCRNN_ERR_UNSUPPORTED;
 }
+
+// The chain above for cell + output head Linear(F -> 1) shared by all nodes (the regression model's `multipMlp` head with one output): the
+// upstream gradient of every state is the rank-1 tensor dH_t[f][n] = w_head[f] dy_t[n], so the launch takes its two factors -- dy [B][T][N]
+// bf16 in the user layout (what autograd hands back for y) and w_head [F] fp32 -- and makes bf16(w_head[f] dy_t[n]) in its epilogue
+// (gcrnn_fused_seq32.h VAR bit 4; instantiations in gcrnn_fused_seq32c.hip): the bits the head's backward kernel stores into dH, without dH or
+// its sequence-major copy. Uniform-weight graphs, persistent form only (a split batch or a rank-1-weighted graph keeps the entry above).
+int gcrnn_seq32c_seed(const uint16_t* dy, int64_t bstride, const float* w, const uint16_t* h, uint16_t* out, int64_t B, int F, int N, hipStream_t st);
+int gcrnn_seq32c_chain(const Seq32Args& sa, int K, int HS, hipStream_t st);
+
+extern "C" int gcrnn_fused_backward_data_wide_head_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t K, int64_t entries, double uniform_w,
+                                                             int img16) {
+  if (img16 != 1) return 0;      // (bit 1: a rank-1-weighted graph)
+  if (!gcrnn_fused_backward_data_wide_supported(B, T, N, F, K, entries, uniform_w, img16, 0)) return 0;
+  if (!seq32_wanted(B)) return 0;      // (a split batch: one launch per step)
+  if (B * T * N * 2 > 2147483647LL) return 0;
+  return 1;
+}
+
+// Contract of gcrnn_fused_backward_data_wide_bf16 with (dy, w_head) in place of dHs: dpre[T-1] = bf16(w_head dy[:, T-1]) (1 - hs[T-1]^2); for
+// t = T-1 .. 1: dpre[t-1] = (gf[t] sum_k (S)^k (dpre[t] B_k) + bf16(w_head dy[:, t-1])) (1 - hs[t-1]^2); dh0 / dgf_parts as there.
+extern "C" int gcrnn_fused_backward_data_wide_head_bf16(const void* dy, const float* w_head, const void* hs, void* dpre, void* dh0, const void* wpackT,
+                                                        const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4, int64_t entries,
+                                                        int64_t B, int64_t T, int64_t N, int64_t F, int64_t K, const float* gf, const void* h0s,
+                                                        float* dgf_parts, void* stream) {
+  if (dgf_parts && !h0s) return GCRNN_ERR_NULL_POINTER;
+  if (!dy || !w_head || !hs || !dpre || !wpackT || !tile_nodes || !tile_off || !ell_col4) return GCRNN_ERR_NULL_POINTER;
+  if (B <= 0 || T <= 0 || N <= 0 || N > NP || B > (1 << 24) || entries <= 0 || entries % 4) return GCRNN_ERR_BAD_SHAPE;
+  if (B * (NP * F * 2) > 2147483647LL || B * T * N * 2 > 2147483647LL || (reinterpret_cast<uintptr_t>(dy) & 1)) return GCRNN_ERR_BAD_SHAPE;
+  if (!seq32_wanted(B) || !seq32_lds_chain(F, K, entries, false)) return GCRNN_ERR_UNSUPPORTED;      // (a split batch, or no such instantiation / no LDS room)
+  const int64_t hstep = B * NP * F;
+  hipStream_t st = as_stream(stream);
+  const int rc = gcrnn_seq32c_seed((const uint16_t*)dy + (T - 1) * N, T * N, w_head, (const uint16_t*)hs + (T - 1) * hstep, (uint16_t*)dpre + (T - 1) * hstep,
+                                   B, (int)F, (int)N, st);
+  if (rc != GCRNN_OK) return rc;
+  const bool fin = dh0 != nullptr || dgf_parts != nullptr;
+  if (T < 2 && !fin) return GCRNN_OK;
+  const int nch = (int)(F / 32);
+  const int64_t gstep = B * (nch * SWAVES);
+  Seq32Args sa{};
+  sa.hfirst = (const uint16_t*)dpre + (T - 1) * hstep;
+  sa.out0 = (uint16_t*)dpre + (T - 2) * hstep; sa.ostride = -hstep;
+  sa.dy0 = T >= 2 ? (const uint16_t*)dy + (T - 2) * N : nullptr; sa.dystride = -N; sa.dybstride = T * N;      // chain step i reads dy[:, T-2-i]
+  sa.head_w = w_head;
+  sa.hs0 = (const uint16_t*)hs + (T - 2) * hstep; sa.hsstride = -hstep;
+  sa.gsc0 = gf ? gf + (T - 1) * B : nullptr; sa.gscstride = -B;
+  sa.gpart0 = dgf_parts ? dgf_parts + (T - 1) * gstep : nullptr; sa.gpartstride = -gstep;
+  sa.final_raw = fin ? 1 : 0; sa.final_out = (uint16_t*)dh0; sa.final_h = dgf_parts ? (const uint16_t*)h0s : nullptr;
+  sa.wpack = (const uint4*)wpackT;
+  sa.tile_nodes = tile_nodes; sa.tile_off = tile_off; sa.ell_col4 = (const uint2*)ell_col4;
+  sa.entries = (int)entries; sa.B = (int)B; sa.N = (int)N;
+  sa.nsteps = (int)(T - 1) + (fin ? 1 : 0);
+  return gcrnn_seq32c_chain(sa, (int)K, nch, st);
+}

@@ -2513,12 +2513,55 @@ def fused_backward_data(dHs, hs, wB, graph, want_dh0=True, gf=None, h0s=None, bi
                                                  B, T, graph.N, F, K, _p(gf), _p(h0s), _p(parts), plan.get('uniform_w', 0.0), _p(dH_user),
                                                  1 if plan16 else 0, st),
               'fused_backward_data')
+    return _chain_results(dpre, dh0, parts, h0s, bias)
+
+
+def _chain_results(dpre, dh0, parts, h0s, bias):
+    """What the data-gradient chains return: (dpre, dh0), and with h0s also d loss / d gf from the launches' partial sums."""
     if h0s is None:
         return dpre, dh0
+    T, B = dpre.shape[0], dpre.shape[1]
     dgf = parts.sum(dim=1).view(T, B)
     if bias is not None:
         dgf = dgf + dpre.sum(dim=2, dtype=torch.float32) @ bias.detach().float().view(-1)
     return dpre, dh0, dgf
+
+
+def fused_backward_data_head_plan(graph, B, T, N, F, K):
+    """The adjoint bf16-image plan when gcrnn_fused_backward_data_wide_head_bf16 takes the problem (uniform-weight graph, persistent form),
+    else None. GCRNN_NO_WIDE_CHAIN=1 switches the wide chain off altogether, this form included."""
+    plan16 = _adjoint_plan16(graph)
+    if plan16 is None or F % 32 != 0 or os.environ.get('GCRNN_NO_WIDE_CHAIN'):
+        return None
+    if not lib.gcrnn_fused_backward_data_wide_head_supported(B, T, N, F, K, int(plan16['entries']), float(plan16.get('uniform_w', 0.0)), 1):
+        return None
+    return plan16
+
+
+def fused_backward_data_head(dy, w_head, hs, wB, graph, want_dh0=True, gf=None, h0s=None, bias=None):
+    """fused_backward_data for cell + output head Linear(F -> 1) shared by all nodes: the upstream gradient of the states is
+    dH[b][t][f][n] = bf16(w_head[f] dy[b][t][n]) -- what the head's backward kernel stores -- and enters as its factors dy [B][T][N] bf16 (user
+    layout) and w_head [F] fp32; the ONE launch of the wide chain makes it in its epilogue (gcrnn_fused_backward_data_wide_head_bf16), so
+    neither dH nor its sequence-major copy is allocated. Same results, bit for bit, as fused_backward_data on that dH. Raises where
+    fused_backward_data_head_plan gives None."""
+    T, B, npad, F = hs.shape
+    K = wB.shape[2]
+    N = graph.N
+    plan16 = fused_backward_data_head_plan(graph, B, T, N, F, K)
+    if plan16 is None:
+        raise GcrnnError('fused_backward_data_head: the wide chain with the head\'s gradient does not take this problem '
+                         '(fused_backward_data_head_plan)')
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and dy.numel() == B * T * N
+    assert w_head.dtype == torch.float32 and w_head.is_contiguous() and w_head.numel() == F
+    st = _stream()
+    wBt = _transposed_taps(wB)                                              # [F_in][1][K][F_out]
+    dpre = torch.empty((T, B, npad, F), dtype=torch.bfloat16, device=hs.device)
+    dh0 = torch.empty((B, npad, F), dtype=torch.bfloat16, device=hs.device) if want_dh0 else None
+    wpw = _fused_pack_weights_wide(wBt.new_zeros((F, 1, K, 0)), wBt, plan16['uniform_w'], st)
+    parts = torch.empty((T * B, (F // 32) * int(lib.gcrnn_fused_step_waves())), dtype=torch.float32, device=hs.device) if h0s is not None else None
+    check(lib.gcrnn_fused_backward_data_wide_head_bf16(_p(dy), _p(w_head), _p(hs), _p(dpre), _p(dh0), _p(wpw), *_wide_graph_args(plan16),
+                                                       B, T, N, F, K, _p(gf), _p(h0s), _p(parts), st), 'fused_backward_data_wide_head')
+    return _chain_results(dpre, dh0, parts, h0s, bias)
 
 
 def fused_backward_weight(dpre, X, H, h0, graph, F, G, K, want_bias=False, gi=None, gf=None, h_is_h0=False, hzero=None):
@@ -2765,13 +2808,10 @@ class _FusedCell(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dH):
         X, h0, wA, wB, bias, H, hs_all, gi, gf, xs = ctx.saved_tensors
-        graph, npad = ctx.graph, ctx.npad
-        B, T, G, N = X.shape
-        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
-        K = max(Kin, Kst)
-        if ctx.needs_input_grad[0] and not fused_input_grad_ok(F, G):
+        graph = ctx.graph
+        K = max(wA.shape[2], wB.shape[2])
+        if ctx.needs_input_grad[0] and not fused_input_grad_ok(wA.shape[0], X.shape[2]):
             raise GcrnnError('the fused BPTT produces the gradient w.r.t. the input sequence X only for G == F')
-        st = _stream()
         hs = hs_all[1:]
         gated = gi is not None
         if gated:
@@ -2779,35 +2819,100 @@ class _FusedCell(torch.autograd.Function):
         dH = dH.to(torch.bfloat16).contiguous()
         dHs, dHu = fused_pack_upstream(dH, graph, K)
         wBk = _pad_tap_count(wB, K)
-        dgf = None
         if gated and ctx.needs_input_grad[6]:
-            dpre, dh0s, dgf = fused_backward_data(dHs, hs, wBk, graph, want_dh0=ctx.needs_input_grad[1], gf=gf,
-                                                  h0s=hs_all[:1], bias=bias, dH_user=dHu)
+            chain = fused_backward_data(dHs, hs, wBk, graph, want_dh0=ctx.needs_input_grad[1], gf=gf,
+                                        h0s=hs_all[:1], bias=bias, dH_user=dHu)
         else:
-            dpre, dh0s = fused_backward_data(dHs, hs, wBk, graph, want_dh0=ctx.needs_input_grad[1], gf=gf if gated else None, dH_user=dHu)
-        want_b = bias is not None and ctx.needs_input_grad[4]
-        dW, dbs = fused_backward_weight(dpre, X, H, h0, graph, F, G, K, want_bias=True,
-                                        gi=gi if gated else None, gf=gf if gated else None)       # [F][K][F+G], [F] fp32
-        gA = dW[:, :Kin, F:].unsqueeze(1).to(wA.dtype) if ctx.needs_input_grad[2] else None
-        gB = dW[:, :Kst, :F].unsqueeze(1).to(wB.dtype) if ctx.needs_input_grad[3] else None
-        gb = dbs.view_as(bias).to(bias.dtype) if want_b else None
-        dgi = None
-        if gated and ctx.needs_input_grad[5]:
-            xsq = xs if xs is not None else fused_pack_inputs(X, h0, graph)[0]
-            dgi = fused_gate_grad(xsq, dpre, wA, bias, graph, K)
-        gh0 = None
-        if ctx.needs_input_grad[1]:
-            gh0 = _unpack_grad(dh0s, B, 1, F, N, st).view(B, F, N).to(h0.dtype)
-        gX = None
-        if ctx.needs_input_grad[0]:
-            # dX_t = gi_t sum_k (dpre_t A_k) shifted k times by S^T: the input filter's adjoint, every item in one launch
-            wAt = _transposed_taps(_pad_tap_count(wA, K))                             # [G][1][K][F]
-            dxs = fused_filter_output(dpre, wAt, None, graph, K, N, adjoint=True)     # [T][B][NPad][G] bf16
-            gX = _unpack_grad(dxs, B, T, G, N, st)
-            if gated:
-                gX = gX * gi.t().reshape(B, T, 1, 1).to(gX.dtype)
-            gX = gX.to(X.dtype)
-        return gX, gh0, gA, gB, gb, dgi, dgf, None, None, None
+            chain = fused_backward_data(dHs, hs, wBk, graph, want_dh0=ctx.needs_input_grad[1], gf=gf if gated else None, dH_user=dHu)
+        return _fused_cell_backward_tail(ctx.needs_input_grad, chain, X, h0, wA, wB, bias, H, gi, gf, xs, graph) + (None, None, None)
+
+
+def _fused_cell_backward_tail(needs, chain, X, h0, wA, wB, bias, H, gi, gf, xs, graph):
+    """Everything of the fused cell's BPTT behind the data-gradient chain (`chain` = its results: dpre, dh0s and, for the forget gates, dgf):
+    the weight-gradient launch, d gi, d h0 and d X. needs[0:7]: which of (X, h0, wA, wB, bias, gi, gf) want a gradient; gi / gf: the detached
+    fp32 gates [T][B] or None. Returns those seven gradients."""
+    dpre, dh0s = chain[0], chain[1]
+    dgf = chain[2] if len(chain) > 2 else None
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    K = max(Kin, Kst)
+    st = _stream()
+    gated = gi is not None
+    want_b = bias is not None and needs[4]
+    dW, dbs = fused_backward_weight(dpre, X, H, h0, graph, F, G, K, want_bias=True,
+                                    gi=gi if gated else None, gf=gf if gated else None)       # [F][K][F+G], [F] fp32
+    gA = dW[:, :Kin, F:].unsqueeze(1).to(wA.dtype) if needs[2] else None
+    gB = dW[:, :Kst, :F].unsqueeze(1).to(wB.dtype) if needs[3] else None
+    gb = dbs.view_as(bias).to(bias.dtype) if want_b else None
+    dgi = None
+    if gated and needs[5]:
+        xsq = xs if xs is not None else fused_pack_inputs(X, h0, graph)[0]
+        dgi = fused_gate_grad(xsq, dpre, wA, bias, graph, K)
+    gh0 = None
+    if needs[1]:
+        gh0 = _unpack_grad(dh0s, B, 1, F, N, st).view(B, F, N).to(h0.dtype)
+    gX = None
+    if needs[0]:
+        # dX_t = gi_t sum_k (dpre_t A_k) shifted k times by S^T: the input filter's adjoint, every item in one launch
+        wAt = _transposed_taps(_pad_tap_count(wA, K))                             # [G][1][K][F]
+        dxs = fused_filter_output(dpre, wAt, None, graph, K, N, adjoint=True)     # [T][B][NPad][G] bf16
+        gX = _unpack_grad(dxs, B, T, G, N, st)
+        if gated:
+            gX = gX * gi.t().reshape(B, T, 1, 1).to(gX.dtype)
+        gX = gX.to(X.dtype)
+    return gX, gh0, gA, gB, gb, dgi, dgf
+
+
+class _FusedCellHead(torch.autograd.Function):
+    """_FusedCell followed by the output head Linear(F -> 1) shared by all nodes (the regression model's `multipMlp` head with one output) as ONE
+    autograd node: y [B*T][1][N] bf16. The forward is the cell's training forward and the head's kernel on H, launch for launch what the two
+    nodes run. The backward never materialises dH: the head's kernel gives d w_head / d b_head alone (no dH store), and the wide chain makes
+    its upstream operand bf16(w_head[f] dy[n]) in its own epilogue (fused_backward_data_head) -- bit for bit the gradients of the two nodes,
+    without dH [B][T][F][N], its sequence-major copy and the traffic of both."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, gi, gf, hw, hb, graph, xs, hs_all):
+        gv = (gi, gf) if gi is not None else None
+        hs_all, plan, H = fused_cell_forward(X, h0, wA, wB, bias, graph, return_states=True, gate_values=gv,
+                                             packed=(xs, hs_all) if xs is not None else None)
+        B, T, F, N = H.shape
+        hwc = hw.contiguous()
+        hbc = hb.contiguous() if hb is not None else None
+        assert hbc is None or hbc.dtype == hwc.dtype
+        y = torch.empty((B * T, 1, N), dtype=torch.bfloat16, device=H.device)
+        check(lib.gcrnn_node_linear_bf16_forward(dtype_code(hwc.dtype), _p(H), _p(hwc), _p(hbc), _p(y), B * T, N, F, 1, _stream()),
+              'node_linear_bf16_forward')
+        ctx.save_for_backward(X, h0, wA, wB, bias, H, hs_all, gi, gf, xs, hwc)
+        ctx.graph = graph
+        ctx.has_head_bias = hb is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        X, h0, wA, wB, bias, H, hs_all, gi, gf, xs, hw = ctx.saved_tensors
+        graph = ctx.graph
+        B, T, F, N = H.shape
+        K = max(wA.shape[2], wB.shape[2])
+        if ctx.needs_input_grad[0] and not fused_input_grad_ok(F, X.shape[2]):
+            raise GcrnnError('the fused BPTT produces the gradient w.r.t. the input sequence X only for G == F')
+        gated = gi is not None
+        if gated:
+            gi, gf = gi.detach().float().contiguous(), gf.detach().float().contiguous()
+        dyc = dy.to(torch.bfloat16).contiguous()
+        # the head's parameter gradients: its backward kernel without the dH store (a null dh: the partial sums are the same)
+        nb = int(lib.gcrnn_node_linear_bf16_blocks(B * T, N))
+        pw = torch.empty((nb, 1, F), dtype=torch.float32, device=H.device)
+        pb = torch.empty((nb, 1), dtype=torch.float32, device=H.device)
+        check(lib.gcrnn_node_linear_bf16_backward(dtype_code(hw.dtype), _p(H), _p(hw), _p(dyc), None, _p(pw), _p(pb), B * T, N, F, 1,
+                                                  _stream()), 'node_linear_bf16_backward')
+        ghw = pw.sum(dim=0).to(hw.dtype) if ctx.needs_input_grad[7] else None
+        ghb = pb.sum(dim=0).to(hw.dtype) if (ctx.has_head_bias and ctx.needs_input_grad[8]) else None
+        w32 = hw.detach().float().reshape(-1).contiguous()
+        wBk = _pad_tap_count(wB, K)
+        want_dgf = gated and ctx.needs_input_grad[6]
+        chain = fused_backward_data_head(dyc, w32, hs_all[1:], wBk, graph, want_dh0=ctx.needs_input_grad[1], gf=gf if gated else None,
+                                         h0s=hs_all[:1] if want_dgf else None, bias=bias if want_dgf else None)
+        return _fused_cell_backward_tail(ctx.needs_input_grad, chain, X, h0, wA, wB, bias, H, gi, gf, xs, graph) + (ghw, ghb, None, None, None)
 
 
 def fused_input_grad_ok(F, G):
@@ -2828,6 +2933,27 @@ def fused_cell_train(X, h0, wA, wB, bias, graph, gates=None):
     gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, gates, graph, hzero, pending=pending)
     assert pending is None or pending.settled                   # (the first pre-pass laid out the rest of X)
     return _FusedCell.apply(X, h0, wA, wB, bias, gi, gf, graph, xs, hs_all)
+
+
+def fused_cell_head_train_supported(graph, B, T, N, F, K, wdtype):
+    """Cell + head Linear(F -> 1) trains as one autograd node (fused_cell_head_train): the head's bf16 kernels take (N, F, 1) with these
+    parameters, and the wide chain takes the head's gradient in its factors (fused_backward_data_head_plan)."""
+    return node_linear_supported(F, 1, torch.bfloat16, N, wdtype) and fused_backward_data_head_plan(graph, B, T, N, F, K) is not None
+
+
+def fused_cell_head_train(X, h0, wA, wB, bias, graph, head_w, head_b, gates=None):
+    """fused_cell_train followed by the output head Linear(F -> 1) shared by all nodes (head_w [1][F], head_b [1] or None; fp32 or bf16):
+    y [B*T][1][N] bf16, the values node_linear gives on the cell's H. One autograd node whose backward skips dH (_FusedCellHead);
+    the time gates enter as in fused_cell_train."""
+    require_device(X, h0, wA, wB, bias, head_w)
+    if gates is None:
+        return _FusedCellHead.apply(X, h0, wA, wB, bias, None, None, head_w, head_b, graph, None, None)
+    with torch.no_grad():
+        xs, hs_all, pending = fused_pack_inputs_gated(X.contiguous(), h0, graph, wA.shape[0], max(wA.shape[2], wB.shape[2]))
+        hzero = fused_h0_zero_flag(h0)
+    gi, gf = fused_train_time_gates(xs, hs_all[:1], X, h0, gates, graph, hzero, pending=pending)
+    assert pending is None or pending.settled                   # (the first pre-pass laid out the rest of X)
+    return _FusedCellHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph, xs, hs_all)
 
 
 def fused_cell_train_with_gates(X, h0, wA, wB, bias, graph, gi, gf):

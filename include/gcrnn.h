@@ -533,6 +533,19 @@ int gcrnn_fused_backward_data_wide_bf16(const void* dHs, const void* hs, void* d
                                         const int32_t* tile_off, const void* ell_col4, int64_t entries, int64_t B, int64_t T, int64_t N,
                                         int64_t F, int64_t K, const float* gf, const void* h0s, float* dgf_parts, const void* dHuser_inline,
                                         const float* rank1_a, const float* rank1_b, void* stream);
+/* The same chain for cell + output head Linear(F -> 1) shared by all nodes (training of the regression model's `multipMlp` head with one
+ * output): the upstream gradient dH_t[f][n] = w_head[f] dy_t[n] enters as its two factors -- dy [B][T][N] bf16 in the user layout (what
+ * autograd hands back for y), w_head [F] fp32 on the device -- and the launch makes bf16(w_head[f] dy_t[n]) in its epilogue: the bits
+ * gcrnn_node_linear_bf16_backward stores into dH (O = 1), so dpre / dh0 / dgf_parts equal gcrnn_fused_backward_data_wide_bf16 on that dH bit
+ * for bit, with neither dH nor dHs in memory. Every other argument as there. The query is 1 exactly when the entry above takes the problem
+ * without the inline pack, the graph is uniform-weight (img16 == 1, not the rank-1 bit), the batch runs the persistent form (a split batch
+ * keeps the entry above) and B*T*N*2 fits 31 bits; the entry returns GCRNN_ERR_UNSUPPORTED otherwise, before any launch. */
+int gcrnn_fused_backward_data_wide_head_supported(int64_t B, int64_t T, int64_t N, int64_t F, int64_t K, int64_t entries, double uniform_w,
+                                                  int img16);
+int gcrnn_fused_backward_data_wide_head_bf16(const void* dy, const float* w_head, const void* hs, void* dpre, void* dh0, const void* wpackT,
+                                             const int32_t* tile_nodes, const int32_t* tile_off, const void* ell_col4, int64_t entries,
+                                             int64_t B, int64_t T, int64_t N, int64_t F, int64_t K, const float* gf, const void* h0s,
+                                             float* dgf_parts, void* stream);
 /* Round 5: the node-gated cell's two state-size passes on the wide kernel (csrc/gcrnn_fused_seq32.h modes 3 and 4; reference
  * Utils/graphML.py:2379-2407, 2420-2423). Until round 4 they ran the 16-feature kernels (gcrnn_fused_filter_output_bf16,
  * gcrnn_fused_node_forward_bf16: 1.45 + 1.75 ms per forward at N = 1000, F = G = 64, K = 5, T = 32, B = 256).
