@@ -235,6 +235,15 @@ class GatedGCRNNforClassification(_GatedGCRNNBase):
             self.outputNN = _build_mlp(self.N * self.F_h, self.dimLayersMLP, self.sigma2, self.sigma3, self.bias)
 
     def forward(self, x, h0):
+        if not self.gnn_head and len(self.dimLayersMLP) == 1 and isinstance(self.outputNN[0], nn.Linear) and \
+                self.outputNN[0].weight.dtype == x.dtype:
+            # the drivers' head (dimLayersMLP = [C]) on a small graph: recurrence and read-out in one launch, BPTT started from dlogits
+            # inside its launch -- neither the T states (inference) nor dH (training) are materialised; None: not that path
+            y = self.stateGCRNN.classify(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)
+            if y is not None:
+                for layer in self.outputNN[1:]:                      # finalNonlinearity, where there is one
+                    y = layer(y)
+                return y
         H = self.stateGCRNN(x, h0, last_only=not torch.is_grad_enabled())     # inference: only the last state is materialised
         h = H.select(1, -1)                                          # reference :1844
         if self.gnn_head:

@@ -412,6 +412,11 @@ class GGCRNNCell(nn.Module):
                 return self._forward_fused_edge(X, h0, last_only=True)
             if self._use_small_edge(X, h0):
                 return self._forward_small_edge(X, h0, last_only=True)
+            if self._use_small(X, h0) and not os.environ.get('GCRNN_NO_SMALL_HEAD') and self._small_last_state_pays(X):
+                # the matrix-core kernel stores the last state alone (ops.small_cell_forward); GCRNN_NO_SMALL_HEAD=1: the slice below (A/B)
+                assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
+                ops.require_device(X, h0, self.weight_A)
+                return self._forward_small(X, h0, last_only=True)
             return self.forward(X, h0)[:, -1:]
         assert h0.shape[0] == X.shape[0]
         ops.require_device(X, h0, self.weight_A)
@@ -714,7 +719,8 @@ class GGCRNNCell(nn.Module):
             return ops.small_edge_cell_train(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, gi, gf)
         return ops.small_edge_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, gi, gf, last_only=last_only)
 
-    def _forward_small(self, X, h0, train=False):
+    def _small_gates(self, X, h0, train=False):
+        """(gi, gf) as the one-launch recurrence takes them: None, [T][B] time gates, or [B][T][N] node gates (times the time gates)."""
         gi, gf = self._small_time_gates(X, h0, train)
         if self.spatial_gating == 'node':
             # node gates (graphML.py:2379-2399) from one batched pass over all t; the recurrence takes them per node,
@@ -726,9 +732,51 @@ class GGCRNNCell(nn.Module):
             nf = self._node_gate(self.GRNN_node_forget, self.GFL_node_forget, Xn, h0n).squeeze(3).permute(2, 0, 1)
             gi = ni if gi is None else ni * gi.t().unsqueeze(2)
             gf = nf if gf is None else nf * gf.t().unsqueeze(2)
+        return gi, gf
+
+    def _forward_small(self, X, h0, train=False, last_only=False):
+        gi, gf = self._small_gates(X, h0, train)
         if train:
             return ops.small_cell_train(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, gi, gf)
-        return ops.small_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, gi, gf)
+        return ops.small_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, gi, gf, last_only=last_only)
+
+    @staticmethod
+    def _small_last_state_pays(X):
+        """Inference with the last-state / no-state store of the matrix-core forward: fp64 at every T, fp32 up to T = 20. The kernel's
+        extended instantiation keeps more scalars alive across the time loop and spills some of them in fp32: 5.5 us per step against 5.1 us,
+        so beyond T = 20 the fp32 inference forward was 2 .. 7 % slower than the all-states launch + slice + Linear and stays there."""
+        return X.dtype != torch.float32 or X.shape[1] <= 20
+
+    def classify(self, X, h0, weight, bias):
+        """Cell + read-out Linear(F N -> C) on the LAST state (the classification model's head with dimLayersMLP = [C], reference
+        architectures.py:1844-1856) inside the small-graph matrix-core launches (ops.small_cell_classify): un-gated, time-gated, node-gated
+        and time+node-gated cells, fp32 / fp64. Inference: one launch for recurrence and logits, no state is stored. Training: the forward
+        launch stores the states BPTT reads and makes the logits; the BPTT launch starts from dlogits, so the zero-filled dH [B][T][F][N]
+        of `H.select(1, -1)` never exists. Returns logits B x C, or None when this cell / input / head does not run on that path (the
+        model then continues on forward()). GCRNN_NO_SMALL_HEAD=1 (read at every call) switches it off: A/B against the two-module path."""
+        if os.environ.get('GCRNN_NO_SMALL_HEAD') or self.graph is None or self._state_padded(X, h0) is not None:
+            return None
+        if weight.dim() != 2 or tuple(weight.shape) != (weight.shape[0], self.F * self.N) or weight.dtype != X.dtype or \
+                (bias is not None and bias.dtype != X.dtype):
+            return None
+        gated = self.time_gating == True or self.spatial_gating is not None  # noqa: E712
+        head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
+        if self._use_small(X, h0):
+            train = False
+        elif self._use_small_training(X, h0):
+            train = True
+        else:
+            return None
+        backward = train or head_grad
+        if not backward and not self._small_last_state_pays(X):
+            return None
+        if not ops.small_head_supported(self.N, self.G, self.F, self.Kin, self.Kst, weight.shape[0], X.dtype, backward, gated,
+                                        dx=backward and X.requires_grad):
+            return None
+        assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
+        ops.require_device(X, h0, self.weight_A)
+        gi, gf = self._small_gates(X, h0, backward)
+        return ops.small_cell_classify(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, gi, gf)
 
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----
     def _use_fused(self, X, h0):

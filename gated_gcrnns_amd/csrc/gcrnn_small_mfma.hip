@@ -24,7 +24,9 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------------
-template <typename T, int MAXT>
+// EXT = false is the plain recurrence that stores every state (head_w / head_b / logits / NC / store are ignored and cost it nothing);
+// EXT = true adds the choice of stored states and the read-out on the last state. The per-step arithmetic is the same code.
+template <typename T, int MAXT, bool EXT>
 __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     const T* __restrict__ X,       // [B][Tn][G][N]
     const T* __restrict__ h0,      // [B][F][N]
@@ -33,9 +35,13 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     const T* __restrict__ bias,    // [F] or null
     const T* __restrict__ gi, const T* __restrict__ gf,       // gates of the input / state filter per (b, t, n) through strides, or null
     const T* __restrict__ Sd,      // [N][N] dense S (row m, column n)
-    T* __restrict__ H,             // [B][Tn][F][N]
+    T* __restrict__ H,             // [B][Tn][F][N] (store == 0), [B][1][F][N] (store == 1) or unused (store == 2)
     int Tn, int N, int G, int F, int Kin, int Kst, int B,
-    int64_t gsb, int64_t gst, int64_t gsn) {     // gate element (b, t, n) sits at b gsb + t gst + n gsn
+    int64_t gsb, int64_t gst, int64_t gsn,       // gate element (b, t, n) sits at b gsb + t gst + n gsn
+    const T* __restrict__ head_w,  // [NC][F N] read-out on the last state (nn.Linear weight, row-major over (f, n)) or null
+    const T* __restrict__ head_b,  // [NC] or null
+    T* __restrict__ logits,        // [B][NC] (with head_w)
+    int NC, int store) {           // store: GCRNN_SMALL_STATES_ALL / _LAST / _NONE
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
   const int K = Kin > Kst ? Kin : Kst;
@@ -145,7 +151,9 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
       outv[q] = acc;
     }
     __syncthreads();                    // every wave is done reading Z_0 (the old state) before it is replaced
-    T* Hout = H + ((size_t)b * Tn + t) * F * N;
+    const bool all = !EXT || store == GCRNN_SMALL_STATES_ALL;
+    const bool keep = all || (store == GCRNN_SMALL_STATES_LAST && t == Tn - 1);
+    T* Hout = H + (all ? (size_t)b * Tn + t : (size_t)b) * F * N;
 #pragma unroll
     for (int q = 0; q < MAXT; ++q) {
       const int tile = wave + q * 16;
@@ -158,11 +166,28 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
         if (f < F && n < N) {
           const T v = outv[q][r];
           Z[(G + f) * Ns + n] = v;
-          Hout[(size_t)f * N + n] = v;
+          if (keep) Hout[(size_t)f * N + n] = v;
         }
       }
     }
     // the x_t copy of the next step touches rows 0..G-1 only; its barrier orders the new state too
+  }
+  if (EXT && head_w) {
+    // ---- read-out on the last state (rows G .. G+F-1 of Z): logits[b][c] = head_w[c] . vec_{F,N}(h_T) + head_b[c].
+    // One wave per class, lanes stride over f N + n (coalesced head_w rows), fixed-order butterfly, lane 0 stores.
+    __syncthreads();
+    const int FN = F * N;
+    for (int c = wave; c < NC; c += 16) {
+      const T* wr = head_w + (size_t)c * FN;
+      T s = T(0);
+      for (int i = lane; i < FN; i += 64) {
+        const int f = i / N, n = i - f * N;
+        s += wr[i] * Z[(G + f) * Ns + n];
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (lane == 0) logits[(size_t)b * NC + c] = s + (head_b ? head_b[c] : T(0));
+    }
   }
 }
 
@@ -195,7 +220,10 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     T* __restrict__ dh0,
     T* __restrict__ dX,             // [B][Tn][G][N] (DX)
     int Tn, int N, int G, int F, int Kin, int Kst, int B,
-    int64_t gsb, int64_t gst, int64_t gsn) {     // gate element (b, t, n) sits at b gsb + t gst + n gsn (dgi / dgf are dense)
+    int64_t gsb, int64_t gst, int64_t gsn,       // gate element (b, t, n) sits at b gsb + t gst + n gsn (dgi / dgf are dense)
+    const T* __restrict__ dlogits,  // dH == null: the upstream gradient is that of a read-out on the last state, [B][NC]
+    const T* __restrict__ head_w,   //             [NC][F N]
+    int NC) {
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
   const int K = Kin > Kst ? Kin : Kst;
@@ -265,12 +293,23 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
   for (int q = 0; q < MAXW; ++q) wacc[q] = acc_t{0, 0, 0, 0};
   T bacc = T(0);
   const int FN = F * N, GN = G * N;
+  if (!dH) {
+    // read-out upstream: dH_t exists at t = Tn-1 only, dH_T[f][n] = sum_c dlogits[b][c] head_w[c][f N + n] (c ascending). It starts
+    // in the carry tile, so every step below sees "no dH_t" and no dH is allocated, zero-filled or read.
+    for (int i = tid; i < FN; i += 1024) {
+      const int f = i / N, n = i - f * N;
+      T s = T(0);
+      for (int c = 0; c < NC; ++c) s += dlogits[(size_t)b * NC + c] * head_w[(size_t)c * FN + i];
+      carry[f * Ns + n] = s;
+    }
+    __syncthreads();
+  }
 
   for (int t = Tn - 1; t >= 0; --t) {
     const T* xt = X + ((size_t)b * Tn + t) * GN;
     const T* hp = (t == 0) ? h0 + (size_t)b * FN : H + ((size_t)b * Tn + t - 1) * FN;
     const T* ht = H + ((size_t)b * Tn + t) * FN;
-    const T* dht = dH + ((size_t)b * Tn + t) * FN;
+    const T* dht = dH ? dH + ((size_t)b * Tn + t) * FN : nullptr;
     if (GATED && tid < 2 * N) {
       const int w = tid >= N, n = tid - w * N;
       gvec[w * Ns + n] = (w ? gf : gi)[b * gsb + t * gst + n * gsn];
@@ -282,7 +321,7 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     for (int i = tid; i < FN; i += 1024) {
       const int f = i / N, n = i - f * N;
       const T h = ht[i];
-      dpre[f * Ns + n] = (dht[i] + carry[f * Ns + n]) * (T(1) - h * h);
+      dpre[f * Ns + n] = ((dht ? dht[i] : T(0)) + carry[f * Ns + n]) * (T(1) - h * h);
     }
     __syncthreads();
     // ---- levels k = 0 .. K-1: dW_k += dpre Z_k^T  |  (gated) ya / yb += W_k Z_k  |  Z_{k+1} = Z_k S
@@ -531,17 +570,21 @@ extern "C" int gcrnn_small_dense_backward_dx_supported(int dtype, int64_t N, int
 template <typename T>
 static int dense_fwd_launch(const void* X, const void* h0, const void* wA, const void* wB, const void* bias, const void* gi,
                             const void* gf, const void* Sd, void* H, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
-                            int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st) {
+                            int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st,
+                            const void* head_w = nullptr, const void* head_b = nullptr, void* logits = nullptr, int64_t NC = 0,
+                            int store = GCRNN_SMALL_STATES_ALL) {
   const int64_t K = Kin > Kst ? Kin : Kst;
   const size_t lds = dense_fwd_lds<T>(N, G, F, K);
   const int64_t ot = ((F + 15) / 16) * ((N + 15) / 16);             // output tiles per step, dealt over 16 waves
-  auto kern = ot <= 16 ? small_dense_fwd_kernel<T, 1> : (ot <= 32 ? small_dense_fwd_kernel<T, 2> : small_dense_fwd_kernel<T, 4>);
+  const bool ext = head_w != nullptr || store != GCRNN_SMALL_STATES_ALL;
+  auto kern = ext ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, true> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, true> : small_dense_fwd_kernel<T, 4, true>))
+                  : (ot <= 16 ? small_dense_fwd_kernel<T, 1, false> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, false> : small_dense_fwd_kernel<T, 4, false>));
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
   kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)wA, (const T*)wB, (const T*)bias, (const T*)gi,
                                       (const T*)gf, (const T*)Sd, (T*)H, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
-                                      (int)B, gsb, gst, gsn);
+                                      (int)B, gsb, gst, gsn, (const T*)head_w, (const T*)head_b, (T*)logits, (int)NC, store);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -565,7 +608,8 @@ template <typename T, bool GATED, bool DX>
 static int dense_bwd_launch(const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
                             const void* bias, const void* gi, const void* gf, const void* Sd, void* pA, void* pB, void* pb,
                             void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
-                            int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st) {
+                            int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st,
+                            const void* dlogits = nullptr, const void* head_w = nullptr, int64_t NC = 0) {
   const size_t lds = dense_bwd_lds<T>(N, G, F, Kin, Kst, GATED, DX);
   const int64_t wt = (Kin > Kst ? Kin : Kst) * ((F + 15) / 16) * ((G + F + 15) / 16);   // weight-gradient tiles, persistent
   auto kern = wt <= 16 ? small_dense_bwd_kernel<T, GATED, 1, DX>
@@ -576,7 +620,7 @@ static int dense_bwd_launch(const void* X, const void* h0, const void* H, const 
   kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)H, (const T*)dH, (const T*)wA, (const T*)wB,
                                       (const T*)bias, (const T*)gi, (const T*)gf, (const T*)Sd, (T*)pA, (T*)pB, (T*)pb,
                                       (T*)dgi, (T*)dgf, (T*)dh0, (T*)dX, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
-                                      (int)B, gsb, gst, gsn);
+                                      (int)B, gsb, gst, gsn, (const T*)dlogits, (const T*)head_w, (int)NC);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -618,5 +662,65 @@ extern "C" int gcrnn_small_dense_backward_dx(int dtype, const void* X, const voi
   if (dtype == GCRNN_F32)
     return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
   return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
+#undef GCRNN_DENSE_BWD_ARGS
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// read-out on the last state (the classification model): logits from the forward launch, BPTT seeded from dlogits
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int gcrnn_small_dense_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t C,
+                                                int backward, int gated, int dx) {
+  if (C <= 0 || C > GCRNN_SMALL_HEAD_MAX_CLASSES) return 0;
+  if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated)) return 0;
+  if (dx && !gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gated)) return 0;
+  return 1;
+}
+
+extern "C" int gcrnn_small_dense_forward_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB,
+                                              const void* bias, const void* gi, const void* gf, const void* Sdense,
+                                              const void* head_w, const void* head_b, void* H, void* logits, int64_t B, int64_t T,
+                                              int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                              int64_t gate_stride_t, int64_t gate_stride_n, int64_t C, int store_states,
+                                              void* stream) {
+  if (!X || !h0 || !wA || !wB || !Sdense) return GCRNN_ERR_NULL_POINTER;
+  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if ((head_w == nullptr) != (logits == nullptr) || (!head_w && head_b)) return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (store_states != GCRNN_SMALL_STATES_ALL && store_states != GCRNN_SMALL_STATES_LAST && store_states != GCRNN_SMALL_STATES_NONE)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (store_states == GCRNN_SMALL_STATES_NONE ? !head_w : !H) return GCRNN_ERR_NULL_POINTER;      // a launch with nothing to write / no H
+  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (head_w ? C <= 0 : C != 0) return GCRNN_ERR_BAD_SHAPE;
+  if (head_w ? !gcrnn_small_dense_head_supported(dtype, N, G, F, Kin, Kst, C, 0, gi != nullptr, 0)
+             : !gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, 0, gi != nullptr))
+    return GCRNN_ERR_UNSUPPORTED;
+  if (dtype == GCRNN_F32)
+    return dense_fwd_launch<float>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
+                                   gate_stride_n, as_stream(stream), head_w, head_b, logits, C, store_states);
+  return dense_fwd_launch<double>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
+                                  gate_stride_n, as_stream(stream), head_w, head_b, logits, C, store_states);
+}
+
+extern "C" int gcrnn_small_dense_backward_head(int dtype, const void* X, const void* h0, const void* H, const void* dlogits,
+                                               const void* head_w, const void* wA, const void* wB, const void* bias,
+                                               const void* gi, const void* gf, const void* Sdense, void* pA, void* pB, void* pb,
+                                               void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T, int64_t N,
+                                               int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                               int64_t gate_stride_t, int64_t gate_stride_n, int64_t C, void* stream) {
+  if (!X || !h0 || !H || !dlogits || !head_w || !wA || !wB || !Sdense || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
+  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0 || C <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_head_supported(dtype, N, G, F, Kin, Kst, C, 1, gi != nullptr, dX != nullptr)) return GCRNN_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+#define GCRNN_DENSE_BWD_ARGS X, h0, H, nullptr, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
+                             gate_stride_b, gate_stride_t, gate_stride_n, st, dlogits, head_w, C
+  if (dtype == GCRNN_F32) {
+    if (dX) return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
+    return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);
+  }
+  if (dX) return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
+  return gi ? dense_bwd_launch<double, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, false>(GCRNN_DENSE_BWD_ARGS);
 #undef GCRNN_DENSE_BWD_ARGS
 }

@@ -2987,16 +2987,19 @@ def _gate_strides(g, B, T, N):
     return T * N, N, 1
 
 
-def small_cell_forward(X, h0, wA, wB, bias, graph, gi=None, gf=None):
+SMALL_STATES_ALL, SMALL_STATES_LAST, SMALL_STATES_NONE = 0, 1, 2      # gcrnn.h: GCRNN_SMALL_STATES_*
+
+
+def small_cell_forward(X, h0, wA, wB, bias, graph, gi=None, gf=None, last_only=False):
     """Whole recurrence in one launch, one workgroup per sequence (small graphs). X: B x T x G x N, h0: B x F x N
     (user layout, fp32 / fp64) -> H: B x T x F x N. gi / gf: gates of the input / state filter or None: [T][B] scalars per
     sequence and step (time gating) or [B][T][N] per node (node gating, or the product of both; matrix-core kernels only).
+    last_only: B x 1 x F x N, the last state -- the matrix-core kernel then stores that state alone (the gather family slices).
     Inference only."""
     require_device(X, h0, wA, wB, bias)
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
     csr = graph.fwd[0]
-    H = torch.empty((B, T, F, N), dtype=X.dtype, device=X.device)
     bvec = bias.detach().contiguous().view(-1) if bias is not None else None
     if gi is not None:
         gi, gf = gi.to(X.dtype).contiguous(), gf.to(X.dtype).contiguous()
@@ -3005,16 +3008,24 @@ def small_cell_forward(X, h0, wA, wB, bias, graph, gi=None, gf=None):
         Sd = graph.dense(X.dtype)
         gs = _gate_strides(gi, B, T, N)
         assert gs == _gate_strides(gf, B, T, N)
+        if last_only:
+            H = torch.empty((B, 1, F, N), dtype=X.dtype, device=X.device)
+            check(lib.gcrnn_small_dense_forward_head(dtype_code(X.dtype), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf),
+                                                     _p(Sd), None, None, _p(H), None, B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2],
+                                                     0, SMALL_STATES_LAST, _stream()), 'small_dense_forward_head')
+            return H
+        H = torch.empty((B, T, F, N), dtype=X.dtype, device=X.device)
         check(lib.gcrnn_small_dense_forward(dtype_code(X.dtype), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf),
                                             _p(Sd), _p(H), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], _stream()),
               'small_dense_forward')
         return H
     assert gi is None or gi.dim() == 2, 'per-node gates need the matrix-core kernels (small_dense_supported)'
+    H = torch.empty((B, T, F, N), dtype=X.dtype, device=X.device)
     check(lib.gcrnn_small_forward(dtype_code(X.dtype), _p(Xc), _p(h0c), _p(wAc),
                                   _p(wBc), _p(bvec), _p(gi), _p(gf), _p(csr.rowptr), _p(csr.col),
                                   _p(vals), _p(H), B, T, N, G, F, Kin, Kst, csr.nnz, _stream()),
           'small_forward')
-    return H
+    return H[:, -1:] if last_only else H
 
 
 def small_training_supported(N, nnz, G, F, Kin, Kst, dtype, E=1):
@@ -3115,6 +3126,105 @@ class _SmallCell(torch.autograd.Function):
 
 def small_cell_train(X, h0, wA, wB, bias, graph, gi=None, gf=None):
     return _SmallCell.apply(X, h0, wA, wB, bias, gi, gf, graph)
+
+
+# ---- the classification model on the matrix-core kernels: read-out Linear(F N -> C) on the last state inside the two launches
+def small_head_supported(N, G, F, Kin, Kst, C, dtype, backward, gated, dx=False):
+    """The matrix-core small-graph kernels take this cell with a read-out of C classes on its last state
+    (gcrnn_small_dense_head_supported; GCRNN_SMALL_GATHER=1 answers no, as for small_dense_supported)."""
+    if not small_dense_supported(N, G, F, Kin, Kst, dtype, backward, gated):
+        return False
+    return bool(lib.gcrnn_small_dense_head_supported(dtype_code(dtype), int(N), int(G), int(F), int(Kin), int(Kst), int(C),
+                                                     int(bool(backward)), int(bool(gated)), int(bool(dx))))
+
+
+def _small_head_forward(X, h0, wA, wB, bias, graph, head_w, head_b, gi, gf, store):
+    """One launch: the recurrence, the states `store` asks for and logits [B][C]. Returns (H or None, logits)."""
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    C = head_w.shape[0]
+    dt, dev = X.dtype, X.device
+    assert tuple(head_w.shape) == (C, F * N) and head_w.dtype == dt and (head_b is None or (head_b.dtype == dt and head_b.numel() == C))
+    H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
+    logits = torch.empty((B, C), dtype=dt, device=dev)
+    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+    if gi is not None:
+        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
+    Xc, h0c, wAc, wBc = X.detach().contiguous(), h0.detach().contiguous(), wA.detach().contiguous(), wB.detach().contiguous()
+    hw = head_w.detach().contiguous()
+    hb = head_b.detach().contiguous() if head_b is not None else None
+    Sd = graph.dense(dt)
+    gs = _gate_strides(gi, B, T, N)
+    assert gs == _gate_strides(gf, B, T, N)
+    check(lib.gcrnn_small_dense_forward_head(dtype_code(dt), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(Sd),
+                                             _p(hw), _p(hb), _p(H), _p(logits), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], C,
+                                             store, _stream()), 'small_dense_forward_head')
+    return H, logits
+
+
+class _SmallCellHead(torch.autograd.Function):
+    """Small-graph cell + Linear(F N -> C) on its last state as ONE autograd node. Forward: one launch that stores every state (BPTT
+    reads them) and makes the logits. Backward: one BPTT launch seeded from dlogits inside the kernel (gcrnn_small_dense_backward_head:
+    no dH [B][T][F][N] is allocated, zero-filled or read) plus the library product for the head's own parameters."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph):
+        X, h0 = X.contiguous(), h0.contiguous()
+        H, logits = _small_head_forward(X, h0, wA, wB, bias, graph, head_w, head_b, gi, gf, SMALL_STATES_ALL)
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, gi, gf, head_w)
+        ctx.graph, ctx.has_hb = graph, head_b is not None
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        X, h0, H, wA, wB, bias, gi, gf, head_w = ctx.saved_tensors
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        C = head_w.shape[0]
+        dt, dev = X.dtype, X.device
+        pA = torch.empty((B, 1, F, Kin, G), dtype=dt, device=dev)
+        pB = torch.empty((B, 1, F, Kst, F), dtype=dt, device=dev)
+        pb = torch.empty((B, F), dtype=dt, device=dev)
+        dgi = dgf = None
+        scalar_gates = gi is not None and gi.dim() == 2
+        if gi is not None:
+            gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
+            dgi = torch.empty((B, T, N), dtype=dt, device=dev)
+            dgf = torch.empty((B, T, N), dtype=dt, device=dev)
+        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+        dX = None
+        if ctx.needs_input_grad[0]:
+            if not small_head_supported(N, G, F, Kin, Kst, C, dt, True, gi is not None, dx=True):
+                raise GcrnnError('small_cell_classify: no gradient for X at this shape (small_head_supported with dx)')
+            dX = torch.empty_like(X)
+        bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+        # every operand is a named local up to the launch (see _SmallCell.backward)
+        dlc, hw, wAc, wBc, Sd = dlogits.contiguous(), head_w.detach().contiguous(), wA.contiguous(), wB.contiguous(), ctx.graph.dense(dt)
+        gs = _gate_strides(gi, B, T, N)
+        check(lib.gcrnn_small_dense_backward_head(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dlc), _p(hw), _p(wAc), _p(wBc), _p(bvec),
+                                                  _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0), _p(dX),
+                                                  B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], C, _stream()),
+              'small_dense_backward_head')
+        if scalar_gates:                                  # a scalar gate collects the gradients of all its nodes
+            dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
+        dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)            # the reductions of _SmallCell.backward, shape for shape
+        dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
+        db = pb.sum(dim=0).view(F, 1) if bias is not None else None
+        dhw = dlc.t().mm(H[:, -1].reshape(B, F * N)) if ctx.needs_input_grad[7] else None
+        dhb = dlc.sum(dim=0) if ctx.has_hb and ctx.needs_input_grad[8] else None
+        return dX, dh0, dwA, dwB, db, dgi, dgf, dhw, dhb, None
+
+
+def small_cell_classify(X, h0, wA, wB, bias, graph, head_w, head_b, gi=None, gf=None):
+    """The small-graph cell followed by Linear(F N -> C) on its last state (head_w [C][F*N], head_b [C] or None, the states' dtype):
+    logits [B][C]. Where nothing wants a gradient it is one launch that stores no state; otherwise one autograd node (_SmallCellHead)
+    with gradients for X (only where wanted: small_head_supported with dx), h0, the taps, the bias, the gates and the head. Shapes:
+    small_head_supported."""
+    require_device(X, h0, wA, wB, bias, head_w)
+    operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
+        return _small_head_forward(X, h0, wA, wB, bias, graph, head_w, head_b, gi, gf, SMALL_STATES_NONE)[1]
+    return _SmallCellHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph)
 
 
 def small_gates_supported(N, G, F, Kin, Kst, dtype, backward):

@@ -772,6 +772,40 @@ int gcrnn_small_dense_backward_dx(int dtype, const void* X, const void* h0, cons
                                   int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
                                   int64_t gate_stride_t, int64_t gate_stride_n, void* stream);
 
+/* The same two kernels with a read-out on the LAST state (the classification model: Linear(F N -> C) on h_T, reference
+ * architectures.py:1844-1856) and with a choice of which states the forward stores.
+ *   head_w [C][F*N] (nn.Linear weight, row-major over (f, n)), head_b [C] or NULL, logits / dlogits [B][C], all of `dtype`:
+ *     logits[b][c] = sum_{f,n} head_w[c][f N + n] h_T[b][f][n] + head_b[c]
+ *   computed by the forward launch from the state still in LDS (one wave per class, fixed-order reduction, no atomics).
+ *   store_states: GCRNN_SMALL_STATES_ALL  H [B][T][F][N], every state (what BPTT reads), bit-identical to gcrnn_small_dense_forward;
+ *                 GCRNN_SMALL_STATES_LAST H [B][1][F][N], h_T only;   GCRNN_SMALL_STATES_NONE  H unused (may be NULL), logits only.
+ * gcrnn_small_dense_forward_head: head_w == NULL means no read-out (then logits and head_b must be NULL, C = 0 and store_states is
+ *   not _NONE): the plain recurrence with a last-state-only store.
+ * gcrnn_small_dense_backward_head: BPTT whose only upstream gradient is dlogits: dH_T[f][n] = sum_c dlogits[b][c] head_w[c][f N + n]
+ *   (c ascending) seeds the carried adjoint inside the launch, so no dH [B][T][F][N] exists. Other arguments and results as
+ *   gcrnn_small_dense_backward; dX [B][T][G][N] or NULL selects the dx variant. The gradients of head_w / head_b are the caller's
+ *   (dlogits^T h_T and the column sums of dlogits).
+ * gcrnn_small_dense_head_supported: 1 <= C <= GCRNN_SMALL_HEAD_MAX_CLASSES (the read-out needs no LDS of its own, the cap only bounds
+ *   the per-workgroup loop) and gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated); with dx also
+ *   gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gated). Answers without a device.
+ * Checked before any launch, in this order: GCRNN_ERR_NULL_POINTER, GCRNN_ERR_BAD_DTYPE, GCRNN_ERR_BAD_SHAPE (also an unknown
+ * store_states), GCRNN_ERR_UNSUPPORTED where the query says no. */
+#define GCRNN_SMALL_HEAD_MAX_CLASSES 1024
+enum { GCRNN_SMALL_STATES_ALL = 0, GCRNN_SMALL_STATES_LAST = 1, GCRNN_SMALL_STATES_NONE = 2 };
+int gcrnn_small_dense_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t C,
+                                     int backward, int gated, int dx);
+int gcrnn_small_dense_forward_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                                   const void* gi, const void* gf, const void* Sdense, const void* head_w, const void* head_b,
+                                   void* H, void* logits, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                   int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t C,
+                                   int store_states, void* stream);
+int gcrnn_small_dense_backward_head(int dtype, const void* X, const void* h0, const void* H, const void* dlogits,
+                                    const void* head_w, const void* wA, const void* wB, const void* bias, const void* gi,
+                                    const void* gf, const void* Sdense, void* pA, void* pB, void* pb, void* dgi, void* dgf,
+                                    void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                    int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t C,
+                                    void* stream);
+
 /* Time gates of the small-graph regime (GGCRNNCell time gating, graphML.py:2248-2278, 2357-2374), both gates in one launch:
  *   gate[g][t][b] = sigmoid( lw_g . vec_{F,N}( tanh(A_g(S) x_t + B_g(S) h0 + 2 b_g) ) + lb_g ),  g = 0 input, 1 forget.
  * Parameters stacked over the two gates: wA2 [2][F][Kin][G], wB2 [2][F][Kst][F], bias2 [2][F] or NULL, lw2 [2][F*N]
