@@ -201,6 +201,16 @@ class GatedGCRNNforRegression(_GatedGCRNNBase):
             y = self.stateGCRNN.train_with_head(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)
             if y is not None:
                 return y
+        if self.mlpType == 'multipMlp' and len(self.dimLayersMLP) == 1 and isinstance(self.outputNN[0], nn.Linear) and \
+                self.outputNN[0].weight.dtype == x.dtype:
+            # the drivers' head (dimLayersMLP = [O]) on a small graph: y_t from the state still in the forward launch's LDS, dH_t formed
+            # inside the BPTT launch -- neither the T states (inference) nor dH (training) are materialised; None: not that path
+            y = self.stateGCRNN.regress(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)      # B x T x O x N
+            if y is not None:
+                y = y.reshape(batchSize, seqLength, -1).unsqueeze(2)
+                for layer in self.outputNN[1:]:                      # finalNonlinearity, where there is one
+                    y = layer(y)
+                return y
         H = self.stateGCRNN(x, h0)                                  # B x T x F_h x N
         flatH = H.reshape(-1, self.F_h, self.N)
         if self.mlpType == 'multipMlp':

@@ -778,6 +778,47 @@ class GGCRNNCell(nn.Module):
         gi, gf = self._small_gates(X, h0, backward)
         return ops.small_cell_classify(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, gi, gf)
 
+    @staticmethod
+    def _small_node_head_pays(X):
+        """Inference with the per-node head inside the matrix-core forward (no state stored) against the all-states launch + node_linear:
+        every shape. Measured at the k-step driver's shape (N = 80, F = 20, K = 5, B = 100), this path / the parent tree, ms:
+        fp32 T = 20 0.190 / 0.197, T = 200 1.793 / 1.807 (device time 1788.0 against 1749.6 + 36.3 us); fp64 T = 20 0.285 / 0.295, T = 200
+        2.749 / 2.792. Unlike the last-state store (_small_last_state_pays) the fp32 forward does not lose beyond T = 20, so nothing is taken
+        off; a row that fails the acceptance rule would be excluded here."""
+        return True
+
+    def regress(self, X, h0, weight, bias):
+        """Cell + output head Linear(F -> O) shared by all nodes on EVERY state (the regression model's `multipMlp` head with
+        dimLayersMLP = [O], reference architectures.py:1616-1627) inside the small-graph matrix-core launches (ops.small_cell_regress):
+        un-gated, time-gated, node-gated and time+node-gated cells, fp32 / fp64. Inference: one launch for recurrence and y, no state is
+        stored. Training: the forward launch stores the states BPTT reads and makes y; the BPTT launch forms dH_t = w^T dy_t itself, so the
+        dH [B][T][F][N] of the two-module path never exists. Returns y B x T x O x N, or None when this cell / input / head does not run on
+        that path (the model then continues on forward()). GCRNN_NO_SMALL_NODE_HEAD=1 (read at every call) switches it off: A/B against the
+        two-module path."""
+        if os.environ.get('GCRNN_NO_SMALL_NODE_HEAD') or self.graph is None or self._state_padded(X, h0) is not None:
+            return None
+        if weight.dim() != 2 or tuple(weight.shape) != (weight.shape[0], self.F) or weight.dtype != X.dtype or \
+                (bias is not None and bias.dtype != X.dtype) or not 0 < weight.shape[0] <= 8:
+            return None
+        gated = self.time_gating == True or self.spatial_gating is not None  # noqa: E712
+        head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
+        if self._use_small(X, h0):
+            train = False
+        elif self._use_small_training(X, h0):
+            train = True
+        else:
+            return None
+        backward = train or head_grad
+        if not backward and not self._small_node_head_pays(X):
+            return None
+        if not ops.small_node_head_supported(self.N, self.G, self.F, self.Kin, self.Kst, weight.shape[0], X.dtype, backward, gated,
+                                             dx=backward and X.requires_grad):
+            return None
+        assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
+        ops.require_device(X, h0, self.weight_A)
+        gi, gf = self._small_gates(X, h0, backward)
+        return ops.small_cell_regress(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, gi, gf)
+
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----
     def _use_fused(self, X, h0):
         if self._wants_grad(X, h0):

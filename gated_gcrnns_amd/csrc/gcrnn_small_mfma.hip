@@ -24,9 +24,14 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------------
-// EXT = false is the plain recurrence that stores every state (head_w / head_b / logits / NC / store are ignored and cost it nothing);
-// EXT = true adds the choice of stored states and the read-out on the last state. The per-step arithmetic is the same code.
-template <typename T, int MAXT, bool EXT>
+// MODE = FWD_PLAIN is the plain recurrence that stores every state (head_w / head_b / logits / NC / store are ignored and cost it nothing);
+// MODE = FWD_LAST adds the choice of stored states and the read-out on the last state; MODE = FWD_NODE has the choice of stored states and
+// the per-node head on EVERY state: Y[b][t][o][n] = sum_f node_w[o][f] h_t[f][n] + node_b[o] (f ascending), with node_w / node_b / Y / O in
+// the places of head_w / head_b / logits / NC. The per-step arithmetic is the same code; the mode is a template parameter because a runtime
+// head branch costs the MAXT = 4 instantiations scratch.
+enum { FWD_PLAIN = 0, FWD_LAST = 1, FWD_NODE = 2 };
+
+template <typename T, int MAXT, int MODE>
 __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     const T* __restrict__ X,       // [B][Tn][G][N]
     const T* __restrict__ h0,      // [B][F][N]
@@ -38,10 +43,11 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     T* __restrict__ H,             // [B][Tn][F][N] (store == 0), [B][1][F][N] (store == 1) or unused (store == 2)
     int Tn, int N, int G, int F, int Kin, int Kst, int B,
     int64_t gsb, int64_t gst, int64_t gsn,       // gate element (b, t, n) sits at b gsb + t gst + n gsn
-    const T* __restrict__ head_w,  // [NC][F N] read-out on the last state (nn.Linear weight, row-major over (f, n)) or null
+    const T* __restrict__ head_w,  // [NC][F N] read-out on the last state (nn.Linear weight, row-major over (f, n)) or null | FWD_NODE: [NC][F]
     const T* __restrict__ head_b,  // [NC] or null
-    T* __restrict__ logits,        // [B][NC] (with head_w)
+    T* __restrict__ logits,        // [B][NC] (with head_w) | FWD_NODE: Y [B][Tn][NC][N]
     int NC, int store) {           // store: GCRNN_SMALL_STATES_ALL / _LAST / _NONE
+  constexpr bool EXT = MODE != FWD_PLAIN;
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
   const int K = Kin > Kst ? Kin : Kst;
@@ -54,9 +60,33 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
   const int F16 = (F + 15) & ~15;
   T* zrow = W + (size_t)F16 * KCs;                 // [Ns] zeros: what masked lanes read
   T* gvec = zrow + Ns;                             // [2][Ns] gates of this step: input-filter | state-filter, per node
+  T* hw = gvec + 2 * Ns;                           // FWD_NODE: [NC][F + 1] the head's weights, its bias in column F (dense_node_head_lds)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int b = blockIdx.x;
+  // FWD_NODE: y_t from h_t in rows G .. G+F-1 of Z, one thread per (o, n) -- consecutive n on consecutive LDS words, hw[o] a broadcast.
+  // The threads are taken from the END of the block: the hop and tap tiles are dealt from wave 0 up, so the last waves have the least to do.
+  // It runs between the barrier on top of step t + 1 and the barrier behind that step's taps, where nothing writes those rows.
+  auto node_head = [&](int t) {
+    T* yt = logits + ((size_t)b * Tn + t) * NC * N;
+    for (int i = 1023 - tid; i < NC * N; i += 1024) {
+      const int o = i / N, n = i - o * N;
+      const T* wr = hw + o * (F + 1);
+      T s = wr[F];                      // the accumulator starts from the bias and takes f in ascending order, as node_linear_fwd_kernel does
+      const T* zr = Z + G * Ns + n;
+      int f = 0;
+      for (; f + 4 <= F; f += 4) {      // eight LDS reads in flight in front of the four dependent multiply-adds (tile_mac's batching)
+        const T w0 = wr[f], w1 = wr[f + 1], w2 = wr[f + 2], w3 = wr[f + 3];
+        const T z0 = zr[f * Ns], z1 = zr[(f + 1) * Ns], z2 = zr[(f + 2) * Ns], z3 = zr[(f + 3) * Ns];
+        s += w0 * z0;
+        s += w1 * z1;
+        s += w2 * z2;
+        s += w3 * z3;
+      }
+      for (; f < F; ++f) s += wr[f] * zr[f * Ns];
+      yt[i] = s;
+    }
+  };
 
   for (int i = tid; i < N4 * Ns; i += 1024) {
     const int m = i / Ns, n = i - m * Ns;
@@ -64,6 +94,11 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
   }
   for (int i = tid; i < KC4 * Ns; i += 1024) Z[i] = T(0);
   for (int i = tid; i < 3 * Ns; i += 1024) zrow[i] = T(0);
+  if (MODE == FWD_NODE)
+    for (int i = tid; i < NC * (F + 1); i += 1024) {
+      const int o = i / (F + 1), f = i - o * (F + 1);
+      hw[i] = f < F ? head_w[(size_t)o * F + f] : (head_b ? head_b[o] : T(0));
+    }
   for (int i = tid; i < F16 * KCs; i += 1024) {
     const int f = i / KCs, kc = i - f * KCs;
     T v = T(0);
@@ -100,6 +135,7 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
       gvec[w * Ns + n] = (w ? gf : gi)[b * gsb + t * gst + n * gsn];
     }
     __syncthreads();
+    if (MODE == FWD_NODE && t > 0) node_head(t - 1);
     // ---- hops: Z_k = Z_{k-1} S
     for (int k = 1; k < K; ++k) {
       const T* zp = Z + (size_t)(k - 1) * C * Ns;
@@ -172,7 +208,11 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     }
     // the x_t copy of the next step touches rows 0..G-1 only; its barrier orders the new state too
   }
-  if (EXT && head_w) {
+  if (MODE == FWD_NODE) {
+    __syncthreads();                    // the last state is in Z
+    node_head(Tn - 1);
+  }
+  if (MODE == FWD_LAST && head_w) {
     // ---- read-out on the last state (rows G .. G+F-1 of Z): logits[b][c] = head_w[c] . vec_{F,N}(h_T) + head_b[c].
     // One wave per class, lanes stride over f N + n (coalesced head_w rows), fixed-order butterfly, lane 0 stores.
     __syncthreads();
@@ -221,9 +261,10 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     T* __restrict__ dX,             // [B][Tn][G][N] (DX)
     int Tn, int N, int G, int F, int Kin, int Kst, int B,
     int64_t gsb, int64_t gst, int64_t gsn,       // gate element (b, t, n) sits at b gsb + t gst + n gsn (dgi / dgf are dense)
-    const T* __restrict__ dlogits,  // dH == null: the upstream gradient is that of a read-out on the last state, [B][NC]
-    const T* __restrict__ head_w,   //             [NC][F N]
-    int NC) {
+    const T* __restrict__ dlogits,  // dH == null, dY == null: the upstream gradient is that of a read-out on the last state, [B][NC]
+    const T* __restrict__ head_w,   //             [NC][F N]   |   with dY: node_w [NC][F]
+    int NC,
+    const T* __restrict__ dY) {     // dH == null: the upstream gradient is that of a per-node head on every state, [B][Tn][NC][N]
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
   const int K = Kin > Kst ? Kin : Kst;
@@ -293,7 +334,7 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
   for (int q = 0; q < MAXW; ++q) wacc[q] = acc_t{0, 0, 0, 0};
   T bacc = T(0);
   const int FN = F * N, GN = G * N;
-  if (!dH) {
+  if (!dH && !dY) {
     // read-out upstream: dH_t exists at t = Tn-1 only, dH_T[f][n] = sum_c dlogits[b][c] head_w[c][f N + n] (c ascending). It starts
     // in the carry tile, so every step below sees "no dH_t" and no dH is allocated, zero-filled or read.
     for (int i = tid; i < FN; i += 1024) {
@@ -310,6 +351,7 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     const T* hp = (t == 0) ? h0 + (size_t)b * FN : H + ((size_t)b * Tn + t - 1) * FN;
     const T* ht = H + ((size_t)b * Tn + t) * FN;
     const T* dht = dH ? dH + ((size_t)b * Tn + t) * FN : nullptr;
+    const T* dyt = dY ? dY + ((size_t)b * Tn + t) * NC * N : nullptr;
     if (GATED && tid < 2 * N) {
       const int w = tid >= N, n = tid - w * N;
       gvec[w * Ns + n] = (w ? gf : gi)[b * gsb + t * gst + n * gsn];
@@ -321,7 +363,12 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     for (int i = tid; i < FN; i += 1024) {
       const int f = i / N, n = i - f * N;
       const T h = ht[i];
-      dpre[f * Ns + n] = ((dht ? dht[i] : T(0)) + carry[f * Ns + n]) * (T(1) - h * h);
+      T d = dht ? dht[i] : T(0);
+      if (dyt) {
+        // per-node head upstream: dH_t[f][n] = sum_o node_w[o][f] dY[b][t][o][n] (o ascending) is formed here and never stored
+        for (int o = 0; o < NC; ++o) d += head_w[(size_t)o * F + f] * dyt[o * N + n];
+      }
+      dpre[f * Ns + n] = (d + carry[f * Ns + n]) * (T(1) - h * h);
     }
     __syncthreads();
     // ---- levels k = 0 .. K-1: dW_k += dpre Z_k^T  |  (gated) ya / yb += W_k Z_k  |  Z_{k+1} = Z_k S
@@ -531,6 +578,11 @@ size_t dense_bwd_lds(int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, 
                       (gated ? (2 + 2 * (size_t)(((int)F + 15) >> 4)) * Ns : 0)) + 16;
 }
 
+// what the per-node head adds to the forward image: node_w [O][F] with node_b in a column of its own (the backward reads node_w from
+// global memory: one value per element and step, next to the dY it multiplies)
+template <typename T>
+size_t dense_node_head_lds(int64_t F, int64_t O) { return sizeof(T) * (size_t)O * (size_t)(F + 1); }
+
 constexpr size_t DENSE_LDS_MAX = 160 * 1024;
 
 template <typename T>
@@ -572,13 +624,14 @@ static int dense_fwd_launch(const void* X, const void* h0, const void* wA, const
                             const void* gf, const void* Sd, void* H, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
                             int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st,
                             const void* head_w = nullptr, const void* head_b = nullptr, void* logits = nullptr, int64_t NC = 0,
-                            int store = GCRNN_SMALL_STATES_ALL) {
+                            int store = GCRNN_SMALL_STATES_ALL, bool node_head = false) {
   const int64_t K = Kin > Kst ? Kin : Kst;
-  const size_t lds = dense_fwd_lds<T>(N, G, F, K);
+  const size_t lds = dense_fwd_lds<T>(N, G, F, K) + (node_head ? dense_node_head_lds<T>(F, NC) : 0);
   const int64_t ot = ((F + 15) / 16) * ((N + 15) / 16);             // output tiles per step, dealt over 16 waves
   const bool ext = head_w != nullptr || store != GCRNN_SMALL_STATES_ALL;
-  auto kern = ext ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, true> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, true> : small_dense_fwd_kernel<T, 4, true>))
-                  : (ot <= 16 ? small_dense_fwd_kernel<T, 1, false> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, false> : small_dense_fwd_kernel<T, 4, false>));
+  auto kern = node_head ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_NODE> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_NODE> : small_dense_fwd_kernel<T, 4, FWD_NODE>))
+              : ext ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_LAST> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_LAST> : small_dense_fwd_kernel<T, 4, FWD_LAST>))
+                    : (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_PLAIN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_PLAIN> : small_dense_fwd_kernel<T, 4, FWD_PLAIN>));
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
@@ -609,7 +662,7 @@ static int dense_bwd_launch(const void* X, const void* h0, const void* H, const 
                             const void* bias, const void* gi, const void* gf, const void* Sd, void* pA, void* pB, void* pb,
                             void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
                             int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st,
-                            const void* dlogits = nullptr, const void* head_w = nullptr, int64_t NC = 0) {
+                            const void* dlogits = nullptr, const void* head_w = nullptr, int64_t NC = 0, const void* dY = nullptr) {
   const size_t lds = dense_bwd_lds<T>(N, G, F, Kin, Kst, GATED, DX);
   const int64_t wt = (Kin > Kst ? Kin : Kst) * ((F + 15) / 16) * ((G + F + 15) / 16);   // weight-gradient tiles, persistent
   auto kern = wt <= 16 ? small_dense_bwd_kernel<T, GATED, 1, DX>
@@ -620,7 +673,7 @@ static int dense_bwd_launch(const void* X, const void* h0, const void* H, const 
   kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)H, (const T*)dH, (const T*)wA, (const T*)wB,
                                       (const T*)bias, (const T*)gi, (const T*)gf, (const T*)Sd, (T*)pA, (T*)pB, (T*)pb,
                                       (T*)dgi, (T*)dgf, (T*)dh0, (T*)dX, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
-                                      (int)B, gsb, gst, gsn, (const T*)dlogits, (const T*)head_w, (int)NC);
+                                      (int)B, gsb, gst, gsn, (const T*)dlogits, (const T*)head_w, (int)NC, (const T*)dY);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -716,6 +769,69 @@ extern "C" int gcrnn_small_dense_backward_head(int dtype, const void* X, const v
   hipStream_t st = as_stream(stream);
 #define GCRNN_DENSE_BWD_ARGS X, h0, H, nullptr, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
                              gate_stride_b, gate_stride_t, gate_stride_n, st, dlogits, head_w, C
+  if (dtype == GCRNN_F32) {
+    if (dX) return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
+    return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);
+  }
+  if (dX) return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
+  return gi ? dense_bwd_launch<double, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, false>(GCRNN_DENSE_BWD_ARGS);
+#undef GCRNN_DENSE_BWD_ARGS
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// per-node head on every state (the regression model's `multipMlp` head): Y from the forward launch, BPTT fed dY and node_w
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int gcrnn_small_dense_node_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t O,
+                                                     int backward, int gated, int dx) {
+  if (O <= 0 || O > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return 0;
+  if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated)) return 0;
+  if (dx && !gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gated)) return 0;
+  if (backward) return 1;               // the backward reads node_w from global memory: the LDS image of the plain backward
+  const int64_t K = Kin > Kst ? Kin : Kst;
+  const size_t lds = dtype == GCRNN_F32 ? dense_fwd_lds<float>(N, G, F, K) + dense_node_head_lds<float>(F, O)
+                                        : dense_fwd_lds<double>(N, G, F, K) + dense_node_head_lds<double>(F, O);
+  return lds <= DENSE_LDS_MAX ? 1 : 0;
+}
+
+extern "C" int gcrnn_small_dense_forward_node_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB,
+                                                   const void* bias, const void* gi, const void* gf, const void* Sdense,
+                                                   const void* node_w, const void* node_b, void* H, void* Y, int64_t B, int64_t T,
+                                                   int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                                   int64_t gate_stride_t, int64_t gate_stride_n, int64_t O, int store_states,
+                                                   void* stream) {
+  if (!X || !h0 || !wA || !wB || !Sdense || !node_w || !Y) return GCRNN_ERR_NULL_POINTER;
+  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (store_states != GCRNN_SMALL_STATES_ALL && store_states != GCRNN_SMALL_STATES_LAST && store_states != GCRNN_SMALL_STATES_NONE)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (store_states != GCRNN_SMALL_STATES_NONE && !H) return GCRNN_ERR_NULL_POINTER;
+  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (O <= 0 || O > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_node_head_supported(dtype, N, G, F, Kin, Kst, O, 0, gi != nullptr, 0)) return GCRNN_ERR_UNSUPPORTED;
+  // the training forward stores the states of the forward-only image; its backward is asked separately
+  if (dtype == GCRNN_F32)
+    return dense_fwd_launch<float>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
+                                   gate_stride_n, as_stream(stream), node_w, node_b, Y, O, store_states, true);
+  return dense_fwd_launch<double>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
+                                  gate_stride_n, as_stream(stream), node_w, node_b, Y, O, store_states, true);
+}
+
+extern "C" int gcrnn_small_dense_backward_node_head(int dtype, const void* X, const void* h0, const void* H, const void* dY,
+                                                    const void* node_w, const void* wA, const void* wB, const void* bias,
+                                                    const void* gi, const void* gf, const void* Sdense, void* pA, void* pB, void* pb,
+                                                    void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T, int64_t N,
+                                                    int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                                    int64_t gate_stride_t, int64_t gate_stride_n, int64_t O, void* stream) {
+  if (!X || !h0 || !H || !dY || !node_w || !wA || !wB || !Sdense || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
+  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (O <= 0 || O > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_node_head_supported(dtype, N, G, F, Kin, Kst, O, 1, gi != nullptr, dX != nullptr)) return GCRNN_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+#define GCRNN_DENSE_BWD_ARGS X, h0, H, nullptr, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
+                             gate_stride_b, gate_stride_t, gate_stride_n, st, nullptr, node_w, O, dY
   if (dtype == GCRNN_F32) {
     if (dX) return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
     return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);

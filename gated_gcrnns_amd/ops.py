@@ -3227,6 +3227,125 @@ def small_cell_classify(X, h0, wA, wB, bias, graph, head_w, head_b, gi=None, gf=
     return _SmallCellHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph)
 
 
+# ---- the regression model on the matrix-core kernels: per-node head Linear(F -> O) on every state inside the two launches
+def small_node_head_supported(N, G, F, Kin, Kst, O, dtype, backward, gated, dx=False):
+    """The matrix-core small-graph kernels take this cell with a per-node head of O outputs on every state
+    (gcrnn_small_dense_node_head_supported; GCRNN_SMALL_GATHER=1 answers no, as for small_dense_supported). backward: the training step,
+    i.e. the forward launch with the head's LDS share and the BPTT launch."""
+    if not small_dense_supported(N, G, F, Kin, Kst, dtype, backward, gated):
+        return False
+    shape = (dtype_code(dtype), int(N), int(G), int(F), int(Kin), int(Kst), int(O))
+    if not lib.gcrnn_small_dense_node_head_supported(*shape, 0, int(bool(gated)), 0):
+        return False
+    return not backward or bool(lib.gcrnn_small_dense_node_head_supported(*shape, 1, int(bool(gated)), int(bool(dx))))
+
+
+def _small_node_head_forward(X, h0, wA, wB, bias, graph, node_w, node_b, gi, gf, store):
+    """One launch: the recurrence, the states `store` asks for and Y [B][T][O][N]. Returns (H or None, Y)."""
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    O = node_w.shape[0]
+    dt, dev = X.dtype, X.device
+    assert tuple(node_w.shape) == (O, F) and node_w.dtype == dt and (node_b is None or (node_b.dtype == dt and node_b.numel() == O))
+    H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
+    Y = torch.empty((B, T, O, N), dtype=dt, device=dev)
+    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+    if gi is not None:
+        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
+    Xc, h0c, wAc, wBc = X.detach().contiguous(), h0.detach().contiguous(), wA.detach().contiguous(), wB.detach().contiguous()
+    nw = node_w.detach().contiguous()
+    nb = node_b.detach().contiguous() if node_b is not None else None
+    Sd = graph.dense(dt)
+    gs = _gate_strides(gi, B, T, N)
+    assert gs == _gate_strides(gf, B, T, N)
+    check(lib.gcrnn_small_dense_forward_node_head(dtype_code(dt), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(Sd),
+                                                  _p(nw), _p(nb), _p(H), _p(Y), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], O,
+                                                  store, _stream()), 'small_dense_forward_node_head')
+    return H, Y
+
+
+class _SmallCellNodeHead(torch.autograd.Function):
+    """Small-graph cell + Linear(F -> O) shared by all nodes on every state as ONE autograd node. Forward: one launch that stores every
+    state (BPTT reads them) and makes Y. Backward: one BPTT launch that forms dH_t = node_w^T dY_t inside the kernel
+    (gcrnn_small_dense_backward_node_head: no dH [B][T][F][N] is allocated, written or read) plus the library products for the head's own
+    parameters."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, gi, gf, node_w, node_b, graph):
+        X, h0 = X.contiguous(), h0.contiguous()
+        H, Y = _small_node_head_forward(X, h0, wA, wB, bias, graph, node_w, node_b, gi, gf, SMALL_STATES_ALL)
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, gi, gf, node_w)
+        ctx.graph, ctx.has_nb = graph, node_b is not None
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, h0, H, wA, wB, bias, gi, gf, node_w = ctx.saved_tensors
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        O = node_w.shape[0]
+        dt, dev = X.dtype, X.device
+        pA = torch.empty((B, 1, F, Kin, G), dtype=dt, device=dev)
+        pB = torch.empty((B, 1, F, Kst, F), dtype=dt, device=dev)
+        pb = torch.empty((B, F), dtype=dt, device=dev)
+        dgi = dgf = None
+        scalar_gates = gi is not None and gi.dim() == 2
+        if gi is not None:
+            gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
+            dgi = torch.empty((B, T, N), dtype=dt, device=dev)
+            dgf = torch.empty((B, T, N), dtype=dt, device=dev)
+        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+        dX = None
+        if ctx.needs_input_grad[0]:
+            if not small_node_head_supported(N, G, F, Kin, Kst, O, dt, True, gi is not None, dx=True):
+                raise GcrnnError('small_cell_regress: no gradient for X at this shape (small_node_head_supported with dx)')
+            dX = torch.empty_like(X)
+        bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+        # every operand is a named local up to the launch (see _SmallCell.backward)
+        dYc, nw, wAc, wBc, Sd = dY.contiguous(), node_w.detach().contiguous(), wA.contiguous(), wB.contiguous(), ctx.graph.dense(dt)
+        gs = _gate_strides(gi, B, T, N)
+        check(lib.gcrnn_small_dense_backward_node_head(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dYc), _p(nw), _p(wAc), _p(wBc), _p(bvec),
+                                                       _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0), _p(dX),
+                                                       B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], O, _stream()),
+              'small_dense_backward_node_head')
+        if scalar_gates:                                  # a scalar gate collects the gradients of all its nodes
+            dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
+        dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)            # the reductions of _SmallCell.backward, shape for shape
+        dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
+        db = pb.sum(dim=0).view(F, 1) if bias is not None else None
+        # d node_w[o][f] = sum_{b,t,n} dY[b][t][o][n] H[b][t][f][n] and d node_b[o] = sum dY: neither makes a [B][T][F][N] temporary
+        dnw = dnb = None
+        want_nb = ctx.has_nb and ctx.needs_input_grad[8]
+        if ctx.needs_input_grad[7] and node_linear_supported(F, O, dt):
+            # node_linear's own backward kernel with dh = NULL: one pass over H and dY into per-block slots. The batched library product
+            # below does the same in 20000 GEMMs of one row at B T = 20000 and measured 375 us against this kernel's 102 us WITH its dh store
+            # (fp32, the k-step driver's shape, T = 200: DESIGN 4.12)
+            nblk = int(lib.gcrnn_node_linear_blocks(B * T, N))
+            pw = torch.empty((nblk, O, F), dtype=dt, device=dev)
+            pnb = torch.empty((nblk, O), dtype=dt, device=dev)
+            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(H), _p(nw), _p(dYc), None, _p(pw), _p(pnb), B * T, N, F, O, _stream()),
+                  'node_linear_backward')
+            dnw = pw.sum(dim=0)
+            dnb = pnb.sum(dim=0) if want_nb else None
+        else:
+            if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B T][O][F] its only temporary
+                dnw = torch.bmm(dYc.view(B * T, O, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
+            dnb = dYc.sum(dim=(0, 1, 3)) if want_nb else None
+        return dX, dh0, dwA, dwB, db, dgi, dgf, dnw, dnb, None
+
+
+def small_cell_regress(X, h0, wA, wB, bias, graph, node_w, node_b, gi=None, gf=None):
+    """The small-graph cell followed by Linear(F -> O) shared by all nodes on every state (node_w [O][F], node_b [O] or None, the states'
+    dtype): Y [B][T][O][N]. Where nothing wants a gradient it is one launch that stores no state; otherwise one autograd node
+    (_SmallCellNodeHead) with gradients for X (only where wanted: small_node_head_supported with dx), h0, the taps, the bias, the gates
+    and the head. Shapes: small_node_head_supported."""
+    require_device(X, h0, wA, wB, bias, node_w)
+    operands = (X, h0, wA, wB, bias, gi, gf, node_w, node_b)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
+        return _small_node_head_forward(X, h0, wA, wB, bias, graph, node_w, node_b, gi, gf, SMALL_STATES_NONE)[1]
+    return _SmallCellNodeHead.apply(X, h0, wA, wB, bias, gi, gf, node_w, node_b, graph)
+
+
 def small_gates_supported(N, G, F, Kin, Kst, dtype, backward):
     if dtype not in (torch.float32, torch.float64) or os.environ.get('GCRNN_SMALL_GATHER'):
         return False

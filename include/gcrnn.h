@@ -806,6 +806,37 @@ int gcrnn_small_dense_backward_head(int dtype, const void* X, const void* h0, co
                                     int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t C,
                                     void* stream);
 
+/* The same two kernels with a per-node head on EVERY state (the regression model's `multipMlp` head with one Linear(F -> O) shared by
+ * all nodes, reference architectures.py:1616-1627).
+ *   node_w [O][F] (nn.Linear weight), node_b [O] or NULL, Y / dY [B][T][O][N], all of `dtype`:
+ *     Y[b][t][o][n] = sum_f node_w[o][f] h_t[b][f][n] + node_b[o]      (from node_b[o], f ascending: gcrnn_node_linear_forward's order and bits)
+ *   computed by the forward launch from each state while it sits in LDS (one thread per (o, n), fixed order, no atomics: two runs give
+ *   the same bits). store_states as above: _ALL for the training forward (H bit-identical to gcrnn_small_dense_forward), _NONE for
+ *   inference (H may be NULL: no state is ever stored), _LAST H [B][1][F][N].
+ * gcrnn_small_dense_backward_node_head: BPTT whose upstream gradient is dY: dH_t[f][n] = sum_o node_w[o][f] dY[b][t][o][n] (o ascending)
+ *   is formed inside the launch at every step, where gcrnn_small_dense_backward reads dH_t, so no dH [B][T][F][N] exists. Other
+ *   arguments and results as gcrnn_small_dense_backward; dX [B][T][G][N] or NULL selects the dx variant. The gradients of node_w /
+ *   node_b are the caller's (sum_{b,t} dY_t H_t^T and the sums of dY).
+ * gcrnn_small_dense_node_head_supported: 1 <= O <= GCRNN_SMALL_NODE_HEAD_MAX_OUT and gcrnn_small_dense_supported(dtype, N, G, F, Kin,
+ *   Kst, backward, gated); with dx also gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gated). backward = 0 also
+ *   asks that the forward's LDS image with the head's O (F + 1) values fits (a training step asks both). Answers without a device.
+ * Checked before any launch, in this order: GCRNN_ERR_NULL_POINTER, GCRNN_ERR_BAD_DTYPE, GCRNN_ERR_BAD_SHAPE (also an unknown
+ * store_states, O <= 0 and O above the maximum), GCRNN_ERR_UNSUPPORTED where the query says no. */
+#define GCRNN_SMALL_NODE_HEAD_MAX_OUT 8
+int gcrnn_small_dense_node_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t O,
+                                          int backward, int gated, int dx);
+int gcrnn_small_dense_forward_node_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                                        const void* gi, const void* gf, const void* Sdense, const void* node_w, const void* node_b,
+                                        void* H, void* Y, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                        int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t O,
+                                        int store_states, void* stream);
+int gcrnn_small_dense_backward_node_head(int dtype, const void* X, const void* h0, const void* H, const void* dY,
+                                         const void* node_w, const void* wA, const void* wB, const void* bias, const void* gi,
+                                         const void* gf, const void* Sdense, void* pA, void* pB, void* pb, void* dgi, void* dgf,
+                                         void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                         int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t O,
+                                         void* stream);
+
 /* Time gates of the small-graph regime (GGCRNNCell time gating, graphML.py:2248-2278, 2357-2374), both gates in one launch:
  *   gate[g][t][b] = sigmoid( lw_g . vec_{F,N}( tanh(A_g(S) x_t + B_g(S) h0 + 2 b_g) ) + lb_g ),  g = 0 input, 1 forget.
  * Parameters stacked over the two gates: wA2 [2][F][Kin][G], wB2 [2][F][Kst][F], bias2 [2][F] or NULL, lw2 [2][F*N]
