@@ -34,17 +34,21 @@ __global__ __launch_bounds__(256) void edge_alpha_kernel(const int32_t* __restri
   T* at = alpha + t * nnz * B + b;
   const T z2 = s2[idx];
   const int j0 = rowptr[m], j1 = rowptr[m + 1];
-  T mx = -INFINITY;
+  T mx = -INFINITY, zmx = T(0);                               // the row's largest activated score and the score it came from
   for (int j = j0; j < j1; ++j) {
     const T z = s1t[(int64_t)col[j] * B] + z2;
     const T e = z > T(0) ? z : slope * z;
-    mx = e > mx ? e : mx;
+    if (e > mx) { mx = e; zmx = z; }
   }
   T den = T(0);
   for (int j = j0; j < j1; ++j) {
     const T z = s1t[(int64_t)col[j] * B] + z2;
     const T e = z > T(0) ? z : slope * z;
-    const T ex = exp_t<T>(e - mx);
+    // On one side of the kink e - mx is the difference of the SCORES times that side's slope: taken before the scaling, it does not carry
+    // the rounding of slope * z at the magnitude of a large common offset (scores near -5000 in fp32: 6e-5 in the exponent)
+    const bool same = (z > T(0)) == (zmx > T(0));
+    const T d = same ? (z > T(0) ? z - zmx : slope * (z - zmx)) : e - mx;
+    const T ex = exp_t<T>(d);
     at[(int64_t)j * B] = ex;
     den += ex;
   }

@@ -474,7 +474,7 @@ __global__ __launch_bounds__(HUB ? 512 : 1024) void edge_att_bwd_kernel(
         d1 += a1r[j] * zf[j];
         d2 += a2r[j] * zf[j];
         gsum += df[j] * rf[j];
-        df[j] = rf[j] > 0.f ? gv * df[j] : 0.f;
+        df[j] = rf[j] > 0.f ? df[j] : 0.f;                    // (gv scales dl and acc below, in fp32: here it would be rounded to bf16)
       }
       d1 = group_sum<LPN>(d1);
       d2 = group_sum<LPN>(d2);
@@ -600,7 +600,7 @@ __global__ __launch_bounds__(HUB ? 512 : 1024) void edge_att_bwd_kernel(
     float ds2 = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
-      const float dl = al[c] * (dal[c] - rsum) * lr[c];
+      const float dl = al[c] * (dal[c] - rsum) * (lr[c] * gv);
       ds2 += dl;
       if (c * LPN + p < dega) Ei[j0a + c * LPN + p] = dl;
     }
@@ -612,7 +612,7 @@ __global__ __launch_bounds__(HUB ? 512 : 1024) void edge_att_bwd_kernel(
         const float lrx = e > 0.f ? 1.f : slope;
         e *= lrx;
         const float alx = eexp(e - sm.z) * sm.w;
-        const float dl = alx * (Ei[j0a + e0 + p] - rsum) * lrx;
+        const float dl = alx * (Ei[j0a + e0 + p] - rsum) * (lrx * gv);
         ds2 += dl;
         Ei[j0a + e0 + p] = dl;
       }
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(HUB ? 512 : 1024) void edge_att_bwd_kernel(
       if (p == 0) sc[m].z = ds2;                              // the row statistics of m are in this group's registers: the slot is free
       float o8[8];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { o8[2 * j] = acc[j].x + a2r[2 * j] * ds2; o8[2 * j + 1] = acc[j].y + a2r[2 * j + 1] * ds2; }
+      for (int j = 0; j < 4; ++j) { o8[2 * j] = gv * acc[j].x + a2r[2 * j] * ds2; o8[2 * j + 1] = gv * acc[j].y + a2r[2 * j + 1] * ds2; }
       dzd[m * LPN + p] = pack8(o8);
     }
     ma = mb; j0a = j0b; dega = degb; zva = zvb; mb = mc; j0b = j0c; degb = degc;

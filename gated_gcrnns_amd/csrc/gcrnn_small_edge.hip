@@ -165,7 +165,7 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
       T mv = (T)(-INFINITY);
       for (int j = j0 + row_lane; j < j1; j += SE_ROW_LANES) {
         const T zz = s1[rcol[j]] + z2;
-        const T e = zz >= T(0) ? zz : T(0.2) * zz;
+        const T e = zz > T(0) ? zz : T(0.2) * zz;
         mv = e > mv ? e : mv;
       }
 #pragma unroll
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
       T d = T(0);
       for (int j = j0 + row_lane; j < j1; j += SE_ROW_LANES) {
         const T zz = s1[rcol[j]] + z2;
-        const T e = zz >= T(0) ? zz : T(0.2) * zz;
+        const T e = zz > T(0) ? zz : T(0.2) * zz;
         d += se_exp<T>(e - mv);
       }
 #pragma unroll
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
     for (int q = tid; q < nnzs; q += SE_THREADS) {
       const int m = tm[q];
       const T zz = s1[tn[q]] + s2[m];
-      const T e = zz >= T(0) ? zz : T(0.2) * zz;
+      const T e = zz > T(0) ? zz : T(0.2) * zz;
       coef[q] = tvl[q] * (se_exp<T>(e - mx[m]) / den[m]);
     }
     __syncthreads();

@@ -7,7 +7,7 @@
 //   dpre = (dH_t + dh) (1 - h_t^2)  -> scratch dPre[b][t] (the input branch's upstream),  dgf[t][b] = sum dpre relu(acc)
 //   dy = gf_t dpre [acc > 0]
 //   column pass^T:   p[q] = coef[q] sum_f dy[f][n_q] Wx[f][m_q]  (= alpha dalpha),   dWx[f][m] = sum_{q in row m} coef[q] dy[f][n_q]
-//   softmax^T:       de[q] = p[q] - alpha[q] sum_{row m_q} p,  dzz = de (zz >= 0 ? 1 : 0.2),  ds1[n] = sum_{column n} dzz,  ds2[m] = sum_{row m} dzz
+//   softmax^T:       de[q] = p[q] - alpha[q] sum_{row m_q} p,  dzz = de (zz > 0 ? 1 : 0.2: the slope at 0 is the negative one, as torch leaky_relu has it),  ds1[n] = sum_{column n} dzz,  ds2[m] = sum_{row m} dzz
 //   folded taps^T:   dwf[r][k][c] += sum_n dwx[r][n] z_k[c][n],  dbf[r] += sum_n dwx[r][n]   (dwx = dWx | ds1 | ds2; registers, all t)
 //   hops^T (Horner): g_{K-1} = dz_{K-1},  g_{k-1} = dz_{k-1} + g_k S^T  with  dz_k[c][n] = sum_r wf[r][k][c] dwx[r][n];  dh <- g_0
 // XP = true, one workgroup per (b, t): the same from x_t with dPre[b][t] as upstream and the gate gi. Without DX it ends at the folded
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
       T mv = (T)(-INFINITY);
       for (int j = j0 + grp_lane; j < j1; j += SEB_ROW_LANES) {
         const T zz = s1[rcol[j]] + z2;
-        const T e = zz >= T(0) ? zz : T(0.2) * zz;
+        const T e = zz > T(0) ? zz : T(0.2) * zz;
         mv = e > mv ? e : mv;
       }
 #pragma unroll
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
       T d = T(0);
       for (int j = j0 + grp_lane; j < j1; j += SEB_ROW_LANES) {
         const T zz = s1[rcol[j]] + z2;
-        const T e = zz >= T(0) ? zz : T(0.2) * zz;
+        const T e = zz > T(0) ? zz : T(0.2) * zz;
         d += seb_exp<T>(e - mv);
       }
       d = seb_group_sum<T>(d);
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     for (int q = tid; q < nnzs; q += SEB_THREADS) {
       const int m = tm[q];
       const T zz = s1[tn[q]] + s2[m];
-      const T e = zz >= T(0) ? zz : T(0.2) * zz;
+      const T e = zz > T(0) ? zz : T(0.2) * zz;
       coef[q] = tvl[q] * (seb_exp<T>(e - mx[m]) / den[m]);
     }
     __syncthreads();
@@ -291,10 +291,10 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     for (int q = tid; q < nnzs; q += SEB_THREADS) {
       const int m = tm[q];
       const T zz = s1[tn[q]] + s2[m];
-      const T e = zz >= T(0) ? zz : T(0.2) * zz;
+      const T e = zz > T(0) ? zz : T(0.2) * zz;
       const T alpha = seb_exp<T>(e - mx[m]) / den[m];
       const T de = pz[q] - alpha * rsum[m];
-      pz[q] = zz >= T(0) ? de : T(0.2) * de;
+      pz[q] = zz > T(0) ? de : T(0.2) * de;
     }
     __syncthreads();
     for (int it = grp; it < 2 * N; it += SEB_THREADS / SEB_ROW_LANES) {

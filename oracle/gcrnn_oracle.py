@@ -81,7 +81,7 @@ def graph_attention(x, a, W, S, negative_slope=0.2):
     a2Wx = np.einsum('kef,bkefn->bken', a2, Wx)                    # :594
     # aWx[m, n] = a1.Wx[:, n] + a2.Wx[:, m]                          :597
     aWx = a1Wx[:, :, :, None, :] + a2Wx[:, :, :, :, None]
-    eij = np.where(aWx >= 0, aWx, negative_slope * aWx)            # :603
+    eij = np.where(aWx > 0, aWx, negative_slope * aWx)             # :603
     mask = (np.sum(np.abs(S), axis=0) > ZERO_TOLERANCE).astype(x.dtype)   # :611-613
     logits = eij * mask - (1.0 - mask) * INFINITE_NUMBER           # :615-618
     logits = logits - logits.max(axis=4, keepdims=True)

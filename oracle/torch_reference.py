@@ -66,7 +66,7 @@ def graph_attention(x, a, W, S, negative_slope=0.2):
     a1Wx = torch.einsum('kef,bkefn->bken', a[:, :, :F], Wx)
     a2Wx = torch.einsum('kef,bkefn->bken', a[:, :, F:], Wx)
     aWx = a1Wx[:, :, :, None, :] + a2Wx[:, :, :, :, None]          # [m, n] = a1.Wx_n + a2.Wx_m
-    eij = torch.where(aWx >= 0, aWx, negative_slope * aWx)
+    eij = torch.where(aWx > 0, aWx, negative_slope * aWx)          # slope at exactly 0: the negative one (nn.functional.leaky_relu)
     mask = (S.abs().sum(dim=0) > ZERO_TOLERANCE).to(x.dtype)
     logits = eij * mask - (1.0 - mask) * INFINITE_NUMBER
     aij = torch.softmax(logits, dim=4) * mask

@@ -242,3 +242,94 @@ def test_the_reference_keeps_its_inputs_dtype():
                        torch.tensor(g['h0'], dtype=torch.float32), True, None)
     assert H.dtype == torch.float32 and H.device.type == 'cpu'
     assert maxdiff(H.double(), g['H']) <= 1e-5
+
+
+# ---------------------------------------------------------------------------------------------- G19: the edge gate's softmax at its extremes
+ATT_REGIMES = ['zero', 'default', 'peaked', 'mixed']
+CELL_SETTINGS = ['zero_zero', 'peaked_peaked', 'zero_peaked', 'default_default']
+VANISHED = 1e-3      # a reference gradient below this share of the SAME gradient's max under the default initialisation counts as vanished (a
+                     # saturated softmax scales it by alpha (1 - alpha)); it is then held absolutely, to the bound times that default-init max
+
+
+def regime_grad_err(g, ref, ref_default):
+    """Max-abs error of one gradient over the magnitude it is held to: its reference's own max, or -- where that has vanished -- the max of the
+    same gradient in the default-init regime (never the vanished gradient's own rounding noise)."""
+    ref, dflt = np.asarray(ref, dtype=np.float64), float(np.max(np.abs(ref_default)))
+    own = float(np.max(np.abs(ref)))
+    scale = own if own >= VANISHED * dflt else dflt
+    g = g.detach().cpu().double().numpy() if isinstance(g, torch.Tensor) else np.asarray(g, dtype=np.float64)
+    assert np.all(np.isfinite(g))
+    return float(np.max(np.abs(g - ref))) / (scale + 1e-300)
+
+
+def test_g19_fixture_is_on_the_dir17_graph_and_holds_the_regimes_it_names():
+    """The stored graph is tests/test_small_edge_train.py::gso_dir17 bit for bit; the zero regime's scores are exactly 0 with Wx != 0, the
+    mixed regime's are exactly 0 on part of the support and of both signs on the rest (exact dyadic operands), and the peaked regimes have
+    at least 30 % of their support rows of two or more entries one-hot to 1e-6."""
+    from test_small_edge_train import gso_dir17
+    g = load_golden('g19_attention_regimes')
+    S = g['S']
+    assert np.array_equal(S, gso_dir17())
+    N = S.shape[1]
+    mask = np.abs(S[0] + np.eye(N)) > tr.ZERO_TOLERANCE
+    assert mask[3].sum() == 0 and mask[5].sum() == 1 and mask[:, 5].sum() == 1 and mask[9].sum() == N - 1      # empty row, isolated node, hub row
+
+    def scores(r):
+        F = r['W'].shape[2]
+        Wx = np.einsum('fg,bgn->bfn', r['W'][0, 0], r['x'])
+        s1, s2 = np.einsum('f,bfn->bn', r['a'][0, 0, :F], Wx), np.einsum('f,bfn->bn', r['a'][0, 0, F:], Wx)
+        return (s1[:, None, :] + s2[:, :, None])[:, mask], Wx
+    z, Wx = scores(g['att_zero'])
+    assert np.all(z == 0) and np.abs(Wx).min() > 0
+    z, _ = scores(g['att_mixed'])
+    assert (z == 0).sum() > 2 * mask.diagonal().sum() and (z > 0).sum() >= 10 and (z < 0).sum() >= 10
+    assert np.array_equal(z * 256, np.round(z * 256))
+    r = g['att_peaked']
+    assert np.array_equal(r['a'], float(g['att_k']) * g['att_default']['a']) and float(g['att_k']) > 1
+    y = tr.graph_attention(t64(r['x']), t64(r['a']), t64(r['W']), t64(S))            # (finite at scores of this size)
+    assert bool(torch.isfinite(y).all())
+    for s in CELL_SETTINGS:
+        p = g['cell_%s_params' % s]
+        for att, kind in zip(('input_attention', 'forget_attention'), s.split('_')):
+            want = {'zero': 0.0, 'peaked': float(g['cell_k']), 'default': 1.0}[kind] * g['cell_default_default_params'][att + '.mixer']
+            assert np.array_equal(p[att + '.mixer'], want), (s, att)
+    b = g['cell_peaked_peaked_params']['bias'][:, 0]
+    for i, att in enumerate(('input_attention', 'forget_attention')):
+        a, W = g['cell_peaked_peaked_params'][att + '.mixer'][0, 0], g['cell_peaked_peaked_params'][att + '.weight'][0, 0]
+        assert abs((a[:7] + a[7:]) @ (W @ b) - g['cell_peaked_offset'][i]) <= 1e-12 * abs(g['cell_peaked_offset'][i])
+
+
+@pytest.mark.parametrize('regime', ATT_REGIMES)
+def test_g19_graph_attention_values_and_gradients(regime):
+    """tr.graph_attention against the reference's graphAttention in every regime: values to 1e-12, the gradients w.r.t. x, a and W to 1e-10
+    of each gradient's max. a = 0 is the LeakyReLU's kink: a derivative of 1 there gives a mixer gradient five times the reference's."""
+    g = load_golden('g19_attention_regimes')
+    r, d = g['att_' + regime], g['att_default']
+    x, a, W = t64(r['x'], True), t64(r['a'], True), t64(r['W'], True)
+    y = tr.graph_attention(x, a, W, t64(g['S']))
+    assert tuple(y.shape) == r['y'].shape and maxdiff(y, r['y']) <= TOL
+    (y * t64(g['att_R'])).sum().backward()
+    for name, got in (('grad_x', x.grad), ('grad_a', a.grad), ('grad_W', W.grad)):
+        e = regime_grad_err(got, r[name], d[name])
+        assert e <= GTOL, (regime, name, e)
+    if regime == 'zero':
+        assert float(np.abs(r['grad_a']).max()) > 0.1                               # (the kink's gradient is not a zero that hides the factor)
+
+
+@pytest.mark.parametrize('setting', CELL_SETTINGS)
+def test_g19_edge_gated_cell_states_and_gradients(setting):
+    """tr.ggcrnn_cell(spatial_gating='edge') against the reference cell with zero / peaked / default mixers: states to 1e-12, every
+    parameter's, h0's and X's gradient to 1e-10 of its max (a vanished one: of its max under the default initialisation)."""
+    g = load_golden('g19_attention_regimes')
+    p = params64(g['cell_%s_params' % setting], True)
+    X, h0 = t64(g['cell_X'], True), t64(g['cell_h0'], True)
+    H = tr.ggcrnn_cell(p, t64(g['S']), X, h0, False, 'edge')
+    assert maxdiff(H, g['cell_%s_H' % setting]) <= TOL
+    (H * t64(g['cell_R'])).sum().backward()
+    ref, dflt = g['cell_%s_grads' % setting], g['cell_default_default_grads']
+    got = {k: v.grad for k, v in p.items()}
+    got.update(h0=h0.grad, X=X.grad)
+    assert set(ref) == set(got) and len(ref) == 9
+    for k in sorted(ref):
+        e = regime_grad_err(got[k], ref[k], dflt[k])
+        assert e <= GTOL, (setting, k, e)
