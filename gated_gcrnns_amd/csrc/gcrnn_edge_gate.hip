@@ -309,7 +309,8 @@ __global__ __launch_bounds__(ETHREADS) void edge_att_fwd_kernel(
     }
     float o8[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { o8[2 * j] = fmaxf(acc[j].x, 0.f); o8[2 * j + 1] = fmaxf(acc[j].y, 0.f); }   // the layer's ReLU (graphML.py:2101)
+    // the layer's ReLU (graphML.py:2101), as torch.relu has it: a NaN stays a NaN (fmaxf(NaN, 0) is 0)
+    for (int j = 0; j < 4; ++j) { o8[2 * j] = acc[j].x <= 0.f ? 0.f : acc[j].x; o8[2 * j + 1] = acc[j].y <= 0.f ? 0.f : acc[j].y; }
     if (MODE == 0) {
       if (valid) oseq[n * LPN + p] = pack8(o8);
     } else {

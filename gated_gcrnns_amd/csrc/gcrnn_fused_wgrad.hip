@@ -182,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void fused_wgrad_kernel(
     o.gcur = 1.f;
     o.gbias = 2.f;                                         // the one bias enters both filters
     if (gw_) { o.gcur = gw_[tx * B + bx]; o.gbias = gi[tx * B + bx] + gf[tx * B + bx]; }
-    o.live = has_tile && (!gw_ || o.gcur > 1e-12f) && !(h_is_h0 && !is_x && hzero && hzero[0] != 0);      // wave-uniform
+    o.live = has_tile && (!gw_ || !(o.gcur <= 1e-12f)) &&!(h_is_h0 && !is_x && hzero && hzero[0] != 0);      // wave-uniform
     const uint16_t* zsrc;
     int zrows;
     if (is_x) { zsrc = Xuser + ((int64_t)bx * Tn + tx) * G * N; zrows = G; }

@@ -56,7 +56,7 @@ template <typename T, typename A, int VEC> __device__ __forceinline__ void gfl_s
 
 // act: 0 identity, 1 ReLU, 2 tanh, 3 sigmoid; the derivative is taken from the activation's OUTPUT
 template <typename A> __device__ __forceinline__ A gfl_act(A v, int act) {
-  if (act == 1) return v > A(0) ? v : A(0);
+  if (act == 1) return v <= A(0) ? A(0) : v;      // (as torch.relu: a NaN stays a NaN)
   if (act == 2) return tanh(v);
   if (act == 3) return A(1) / (A(1) + exp(-v));
   return v;

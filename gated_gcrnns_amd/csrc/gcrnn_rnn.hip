@@ -19,7 +19,7 @@ constexpr int RNN_GEMM_THREADS = 256, RNN_GEMM_M = 64, RNN_GEMM_N = 64, RNN_GEMM
 constexpr int RNN_WG_THREADS = 256, RNN_WG_ROWS = 32;
 
 template <typename A> __device__ __forceinline__ A rnn_act(A z, int relu) {
-  if (relu) return z > A(0) ? z : A(0);
+  if (relu) return z <= A(0) ? A(0) : z;      // (as torch.relu: a NaN stays a NaN)
   return tanh(z);
 }
 template <typename A> __device__ __forceinline__ A rnn_act_grad(A h, int relu) {

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
         const T* wr = wx + of[p] * N;
         T acc = T(0);
         for (int q = trp[n]; q < trp[n + 1]; ++q) acc += coef[q] * wr[tm[q]];
-        const T y = g * (acc > T(0) ? acc : T(0));
+        const T y = g * (acc <= T(0) ? T(0) : acc);      // (relu as torch has it: a NaN stays a NaN)
         if (XP) {
           out[i] = y;
         } else {

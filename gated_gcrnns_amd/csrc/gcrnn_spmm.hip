@@ -55,6 +55,10 @@ __device__ __forceinline__ float act_tanh(float x) {      // 1 - 2 / (1 + exp(2x
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
 }
 __device__ __forceinline__ double act_tanh(double x) { return tanh(x); }
+// One rounding per term in EVERY column of a lane's vector: a column's result must not depend on where in the vector it sits
+// (tests/test_sequence_isolation.py, the reversed batch).
+__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 constexpr int STAGE = 128;       // CSR entries staged per trip and wave
 constexpr int WAVES = 4;         // waves per workgroup
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(64 * WAVES) void spmm_stream_kernel(
           A xe[VE];
           unpack16(xv[u], xe, T());
 #pragma unroll
-          for (int e = 0; e < VE; ++e) acc[e] += w[u] * xe[e];
+          for (int e = 0; e < VE; ++e) acc[e] = fma_t(w[u], xe[e], acc[e]);      // (explicit: left to contraction, hipcc fused e = 0, 1 and not e = 2, 3)
         }
       }
     }

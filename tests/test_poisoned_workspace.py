@@ -379,9 +379,10 @@ def _native_stack(c, p):
     return {'H1': hs1.permute(1, 0, 3, 2)[..., :c.N].contiguous(), 'H': H}
 
 
-def _run_kernels(c):
-    """What assert_independent_of_workspace runs under each fill."""
-    p = _build(c)
+def _run_kernels(c, p=None):
+    """What assert_independent_of_workspace runs under each fill. p: a problem built before (tests/test_sequence_isolation.py runs one build
+    several times, on inputs of its own)."""
+    p = _build(c) if p is None else p
     cell, X, h0 = p.cell, p.X, p.h0
     if c.mode == 'infer':
         with torch.no_grad():
@@ -851,6 +852,14 @@ def _rel_check(tag, got, ref, tol, floor=0.0, absolute=()):
         assert e <= t * sc + 1e-300, (tag, k, e / max(sc, 1e-300), t)
 
 
+def _edit(edit, **operands):
+    """run(edit=...) of the makers below: edit({name: device operand}) may write into the operands before the op runs (the data operands
+    only; tests/test_sequence_isolation.py puts one non-finite element there). Without it the operands are the seeded ones."""
+    if edit is not None:
+        with torch.no_grad():
+            edit(operands)
+
+
 def _op_graph_filter_layer(Fin, Fout, K, prec):
     """graph_filter_layer forward and backward at N = 59 (the epicenter graph): taps-first (F_out < F_in) and hops-first, at the bounds of
     tests/test_gnn_heads.py: bf16 x with fp32 parameters 1e-4 (dx, stored in bf16: 1e-2), fp32 1e-5, fp64 1e-11, of max(1, max|ref|)."""
@@ -870,10 +879,11 @@ def _op_graph_filter_layer(Fin, Fout, K, prec):
         dy = torch.randn(items, Fout, N, generator=g, dtype=torch.float64).to(wdt)
         return x, w, b, dy
 
-    def run():
+    def run(edit=None):
         graph = GraphOperator(S, device=DEV)
         assert ops.graph_filter_layer_supported(xdt, wdt, graph, Fin, Fout, K)
         x, w, b, dy = (t.to(DEV) for t in operands())
+        _edit(edit, x=x)
         for t in (x, w, b):
             t.requires_grad_(True)
         y = ops.graph_filter_layer(x, w, b, graph, 'tanh')
@@ -906,9 +916,10 @@ def _op_node_linear(R, F, N, O, prec):
         return (torch.randn(R, F, N, generator=g).to(dt), (torch.randn(O, F, generator=g) / F ** 0.5).to(dt), torch.randn(O, generator=g).to(dt),
                 (0.5 + torch.randn(R, O, N, generator=g)).to(dt))
 
-    def run():
+    def run(edit=None):
         assert ops.node_linear_supported(F, O, dt, N, dt)
         h, w, b, dy = (t.to(DEV) for t in operands())
+        _edit(edit, h=h)
         for t in (h, w, b):
             t.requires_grad_(True)
         y = ops.node_linear(h, w, b)
@@ -930,10 +941,11 @@ def _op_rnn_sequence(B, T, D, Fh, bias, prec):
     dt = {'f32': torch.float32, 'f64': torch.float64}[prec]
     names = ('x', 'h0', 'w_ih', 'w_hh', 'b_ih', 'b_hh')
 
-    def run():
+    def run(edit=None):
         from test_rnn_baseline import _case
         assert ops.rnn_supported(dt, B, T, D, Fh)
         ts, ks, Rr = _case(B, T, D, Fh, 'tanh', bias, dt, seed=B * 1000 + T * 10 + Fh)
+        _edit(edit, x=ks[0], h0=ks[1])
         H = ops.rnn_sequence(*ks, 'tanh')
         (H * Rr.to(dt)).sum().backward()
         out = {'H': H.detach()}
@@ -963,8 +975,9 @@ def _op_l1_loss(shape, prec):
         y.view(-1)[::7] = x.view(-1)[::7]
         return x, y
 
-    def run():
+    def run(edit=None):
         x, y = (t.to(DEV).requires_grad_(True) for t in operands())
+        _edit(edit, x=x)
         loss = ops.l1_loss(x, y)
         (3.0 * loss).backward()
         return {'loss': loss.detach(), 'dx': x.grad, 'dy': y.grad}
@@ -989,8 +1002,9 @@ def _op_batch_time_mse(prec):
         g = torch.Generator().manual_seed(13)
         return torch.randn(65, 1000, generator=g, dtype=torch.float64).to(dt), torch.randn(65, 1000, generator=g, dtype=torch.float64).to(dt)
 
-    def run():
+    def run(edit=None):
         x, y = (t.to(DEV) for t in operands())
+        _edit(edit, x=x)
         return {'metric': ops.batch_time_mse(x, y)}
 
     def check(got):
@@ -1004,10 +1018,11 @@ def _op_cross_entropy(B, C, tag):
     """cross_entropy with hits against fp64 on the host (tests/test_cross_entropy.py, its _check)."""
     from gated_gcrnns_amd import ops
 
-    def run():
+    def run(edit=None):
         from test_cross_entropy import DTYPES, _problem
         z, lab = _problem(B, C, DTYPES[tag], 100 * B + C)
         zd = z.to(DEV).requires_grad_(True)
+        _edit(edit, z=zd)
         loss, hits = ops.cross_entropy(zd, lab.to(DEV), return_hits=True)
         loss.backward()
         return {'loss': loss.detach(), 'hits': hits, 'dz': zd.grad}
@@ -1036,9 +1051,10 @@ def _op_edge_attention(prec):
         mk = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64).to(DEV).to(dt).to(dtype)
         return mk(Tn, N, B, F), mk(Tn, N, B), mk(Tn, N, B), mk(Tn, N, B, F)
 
-    def run():
+    def run(edit=None):
         graph = GraphOperator(S[None], device=DEV)
         Wx, s1, s2, r = operands(dt)
+        _edit(edit, Wx=Wx)
         for t in (Wx, s1, s2):
             t.requires_grad_(True)
         y = ops.edge_attention(Wx, s1, s2, graph)
@@ -1073,8 +1089,9 @@ def _op_lsigf_two_edge_features(prec):
         return (torch.randn(F, E, K, G, generator=g, dtype=torch.float64).div(np.sqrt(G * K * E)).to(dt), torch.randn(B, G, N, generator=g, dtype=torch.float64).to(dt),
                 torch.randn(F, 1, generator=g, dtype=torch.float64).to(dt), torch.randn(B, F, N, generator=g, dtype=torch.float64).to(dt))
 
-    def run():
+    def run(edit=None):
         h, x, b, dy = (t.to(DEV) for t in operands())
+        _edit(edit, x=x)
         for t in (h, x, b):
             t.requires_grad_(True)
         y = gml.LSIGF(h, torch.tensor(S, dtype=dt, device=DEV), x, b)
