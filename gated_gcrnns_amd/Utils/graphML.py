@@ -754,10 +754,20 @@ class GGCRNNCell(nn.Module):
         launch stores the states BPTT reads and makes the logits; the BPTT launch starts from dlogits, so the zero-filled dH [B][T][F][N]
         of `H.select(1, -1)` never exists. Returns logits B x C, or None when this cell / input / head does not run on that path (the
         model then continues on forward()). GCRNN_NO_SMALL_HEAD=1 (read at every call) switches it off: A/B against the two-module path."""
-        if os.environ.get('GCRNN_NO_SMALL_HEAD') or self.graph is None or self._state_padded(X, h0) is not None:
+        route = self._small_head_route(X, h0, weight, bias, 'GCRNN_NO_SMALL_HEAD', lambda w: w.shape[1] == self.F * self.N,
+                                       self._small_last_state_pays, ops.small_head_supported)
+        if route is None:
             return None
-        if weight.dim() != 2 or tuple(weight.shape) != (weight.shape[0], self.F * self.N) or weight.dtype != X.dtype or \
-                (bias is not None and bias.dtype != X.dtype):
+        return ops.small_cell_classify(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
+
+    def _small_head_route(self, X, h0, weight, bias, off_switch, weight_ok, pays, supported):
+        """Whether a head inside the small-graph matrix-core launches takes this cell, input and head (classify, regress): None to decline,
+        else (backward, gi, gf) -- whether the BPTT launch may follow, and the gates as the launches take them. off_switch: the environment
+        variable that declines; weight_ok: the head's test of its 2-D weight; pays: where the inference launch beats the two-module path;
+        supported: the ops query of the head's shapes."""
+        if os.environ.get(off_switch) or self.graph is None or self._state_padded(X, h0) is not None:
+            return None
+        if weight.dim() != 2 or not weight_ok(weight) or weight.dtype != X.dtype or (bias is not None and bias.dtype != X.dtype):
             return None
         gated = self.time_gating == True or self.spatial_gating is not None  # noqa: E712
         head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
@@ -768,15 +778,13 @@ class GGCRNNCell(nn.Module):
         else:
             return None
         backward = train or head_grad
-        if not backward and not self._small_last_state_pays(X):
+        if not backward and not pays(X):
             return None
-        if not ops.small_head_supported(self.N, self.G, self.F, self.Kin, self.Kst, weight.shape[0], X.dtype, backward, gated,
-                                        dx=backward and X.requires_grad):
+        if not supported(self.N, self.G, self.F, self.Kin, self.Kst, weight.shape[0], X.dtype, backward, gated, dx=backward and X.requires_grad):
             return None
         assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
         ops.require_device(X, h0, self.weight_A)
-        gi, gf = self._small_gates(X, h0, backward)
-        return ops.small_cell_classify(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, gi, gf)
+        return (backward,) + self._small_gates(X, h0, backward)
 
     @staticmethod
     def _small_node_head_pays(X):
@@ -795,29 +803,11 @@ class GGCRNNCell(nn.Module):
         dH [B][T][F][N] of the two-module path never exists. Returns y B x T x O x N, or None when this cell / input / head does not run on
         that path (the model then continues on forward()). GCRNN_NO_SMALL_NODE_HEAD=1 (read at every call) switches it off: A/B against the
         two-module path."""
-        if os.environ.get('GCRNN_NO_SMALL_NODE_HEAD') or self.graph is None or self._state_padded(X, h0) is not None:
+        route = self._small_head_route(X, h0, weight, bias, 'GCRNN_NO_SMALL_NODE_HEAD', lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
+                                       self._small_node_head_pays, ops.small_node_head_supported)
+        if route is None:
             return None
-        if weight.dim() != 2 or tuple(weight.shape) != (weight.shape[0], self.F) or weight.dtype != X.dtype or \
-                (bias is not None and bias.dtype != X.dtype) or not 0 < weight.shape[0] <= 8:
-            return None
-        gated = self.time_gating == True or self.spatial_gating is not None  # noqa: E712
-        head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
-        if self._use_small(X, h0):
-            train = False
-        elif self._use_small_training(X, h0):
-            train = True
-        else:
-            return None
-        backward = train or head_grad
-        if not backward and not self._small_node_head_pays(X):
-            return None
-        if not ops.small_node_head_supported(self.N, self.G, self.F, self.Kin, self.Kst, weight.shape[0], X.dtype, backward, gated,
-                                             dx=backward and X.requires_grad):
-            return None
-        assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
-        ops.require_device(X, h0, self.weight_A)
-        gi, gf = self._small_gates(X, h0, backward)
-        return ops.small_cell_regress(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, gi, gf)
+        return ops.small_cell_regress(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
 
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----
     def _use_fused(self, X, h0):

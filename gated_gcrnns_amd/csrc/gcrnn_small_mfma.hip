@@ -619,27 +619,60 @@ extern "C" int gcrnn_small_dense_backward_dx_supported(int dtype, int64_t N, int
   return lds <= DENSE_LDS_MAX ? 1 : 0;
 }
 
+// One forward launch, filled by field name at each entry. The head: the read-out head_w [NC][F N], head_b [NC], out = logits [B][NC]
+// (FWD_LAST), or node_w [NC][F], node_b [NC], out = Y [B][T][NC][N] (FWD_NODE).
+struct DenseFwdArgs {
+  const void *X, *h0, *wA, *wB, *bias, *gi, *gf, *Sd;
+  void* H;
+  int64_t B, T, N, G, F, Kin, Kst, gsb, gst, gsn;
+  hipStream_t st;
+  const void *head_w = nullptr, *head_b = nullptr;
+  void* out = nullptr;
+  int64_t NC = 0;
+  int store = GCRNN_SMALL_STATES_ALL;
+};
+
+// One BPTT launch. The upstream gradient: dH [B][T][F][N]; or dlogits [B][NC] with head_w [NC][F N] (read-out on the last state); or
+// dY [B][T][NC][N] with head_w = node_w [NC][F] (per-node head). dX == nullptr selects the plain variant.
+struct DenseBwdArgs {
+  const void *X, *h0, *H, *wA, *wB, *bias, *gi, *gf, *Sd;
+  void *pA, *pB, *pb, *dgi, *dgf, *dh0, *dX;
+  int64_t B, T, N, G, F, Kin, Kst, gsb, gst, gsn;
+  hipStream_t st;
+  const void *dH = nullptr, *dlogits = nullptr, *dY = nullptr, *head_w = nullptr;
+  int64_t NC = 0;
+};
+
+// What the entries share, in the order they ask it: a gate comes with its partner and, in a backward pass (want_dg), with room for both
+// gate gradients; the dtype where the entry answers for it itself (own_dtype: all but gcrnn_small_dense_forward / _backward, which leave it
+// to the support query and so answer UNSUPPORTED). Then B and T positive, B a grid size: apart, two entries check their store mode first.
+static int dense_shared_status(const void* gi, const void* gf, bool want_dg, const void* dgi, const void* dgf, bool own_dtype, int dtype) {
+  if ((gi == nullptr) != (gf == nullptr) || (want_dg && gi && (!dgi || !dgf))) return GCRNN_ERR_NULL_POINTER;
+  return own_dtype && dtype != GCRNN_F32 && dtype != GCRNN_F64 ? GCRNN_ERR_BAD_DTYPE : GCRNN_OK;
+}
+static bool dense_bt_ok(int64_t B, int64_t T) { return B > 0 && T > 0 && B <= 2147483647LL; }
+
 template <typename T>
-static int dense_fwd_launch(const void* X, const void* h0, const void* wA, const void* wB, const void* bias, const void* gi,
-                            const void* gf, const void* Sd, void* H, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
-                            int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st,
-                            const void* head_w = nullptr, const void* head_b = nullptr, void* logits = nullptr, int64_t NC = 0,
-                            int store = GCRNN_SMALL_STATES_ALL, bool node_head = false) {
-  const int64_t K = Kin > Kst ? Kin : Kst;
-  const size_t lds = dense_fwd_lds<T>(N, G, F, K) + (node_head ? dense_node_head_lds<T>(F, NC) : 0);
+static int dense_fwd_launch(const DenseFwdArgs& a, int mode) {
+  const int64_t N = a.N, F = a.F, K = a.Kin > a.Kst ? a.Kin : a.Kst;
+  const size_t lds = dense_fwd_lds<T>(N, a.G, F, K) + (mode == FWD_NODE ? dense_node_head_lds<T>(F, a.NC) : 0);
   const int64_t ot = ((F + 15) / 16) * ((N + 15) / 16);             // output tiles per step, dealt over 16 waves
-  const bool ext = head_w != nullptr || store != GCRNN_SMALL_STATES_ALL;
-  auto kern = node_head ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_NODE> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_NODE> : small_dense_fwd_kernel<T, 4, FWD_NODE>))
-              : ext ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_LAST> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_LAST> : small_dense_fwd_kernel<T, 4, FWD_LAST>))
-                    : (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_PLAIN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_PLAIN> : small_dense_fwd_kernel<T, 4, FWD_PLAIN>));
+  auto kern = mode == FWD_NODE ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_NODE> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_NODE> : small_dense_fwd_kernel<T, 4, FWD_NODE>))
+              : mode == FWD_LAST ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_LAST> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_LAST> : small_dense_fwd_kernel<T, 4, FWD_LAST>))
+                                 : (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_PLAIN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_PLAIN> : small_dense_fwd_kernel<T, 4, FWD_PLAIN>));
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
-  kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)wA, (const T*)wB, (const T*)bias, (const T*)gi,
-                                      (const T*)gf, (const T*)Sd, (T*)H, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
-                                      (int)B, gsb, gst, gsn, (const T*)head_w, (const T*)head_b, (T*)logits, (int)NC, store);
+  kern<<<(unsigned)a.B, 1024, lds, a.st>>>((const T*)a.X, (const T*)a.h0, (const T*)a.wA, (const T*)a.wB, (const T*)a.bias, (const T*)a.gi,
+                                          (const T*)a.gf, (const T*)a.Sd, (T*)a.H, (int)a.T, (int)N, (int)a.G, (int)F, (int)a.Kin, (int)a.Kst,
+                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.head_w, (const T*)a.head_b, (T*)a.out, (int)a.NC, a.store);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
+}
+
+// The one place that picks the forward instantiation: <T> here, MAXT and the mode (FWD_PLAIN / FWD_LAST / FWD_NODE) in the launcher.
+static int dense_fwd_run(int dtype, const DenseFwdArgs& a, int mode) {
+  return dtype == GCRNN_F32 ? dense_fwd_launch<float>(a, mode) : dense_fwd_launch<double>(a, mode);
 }
 
 extern "C" int gcrnn_small_dense_forward(int dtype, const void* X, const void* h0, const void* wA, const void* wB,
@@ -647,22 +680,18 @@ extern "C" int gcrnn_small_dense_forward(int dtype, const void* X, const void* h
                                          int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
                                          int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, void* stream) {
   if (!X || !h0 || !wA || !wB || !Sdense || !H) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (B <= 0 || T <= 0 || B > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
+  if (int s = dense_shared_status(gi, gf, false, nullptr, nullptr, false, dtype)) return s;
+  if (!dense_bt_ok(B, T)) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, 0, gi != nullptr)) return GCRNN_ERR_UNSUPPORTED;
-  if (dtype == GCRNN_F32)
-    return dense_fwd_launch<float>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b,
-                                   gate_stride_t, gate_stride_n, as_stream(stream));
-  return dense_fwd_launch<double>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
-                                  gate_stride_n, as_stream(stream));
+  const DenseFwdArgs a{.X = X, .h0 = h0, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .H = H, .B = B, .T = T, .N = N,
+                       .G = G, .F = F, .Kin = Kin, .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n,
+                       .st = as_stream(stream)};
+  return dense_fwd_run(dtype, a, FWD_PLAIN);
 }
 
 template <typename T, bool GATED, bool DX>
-static int dense_bwd_launch(const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
-                            const void* bias, const void* gi, const void* gf, const void* Sd, void* pA, void* pB, void* pb,
-                            void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
-                            int64_t Kin, int64_t Kst, int64_t gsb, int64_t gst, int64_t gsn, hipStream_t st,
-                            const void* dlogits = nullptr, const void* head_w = nullptr, int64_t NC = 0, const void* dY = nullptr) {
+static int dense_bwd_launch(const DenseBwdArgs& a) {
+  const int64_t N = a.N, G = a.G, F = a.F, Kin = a.Kin, Kst = a.Kst;
   const size_t lds = dense_bwd_lds<T>(N, G, F, Kin, Kst, GATED, DX);
   const int64_t wt = (Kin > Kst ? Kin : Kst) * ((F + 15) / 16) * ((G + F + 15) / 16);   // weight-gradient tiles, persistent
   auto kern = wt <= 16 ? small_dense_bwd_kernel<T, GATED, 1, DX>
@@ -670,12 +699,23 @@ static int dense_bwd_launch(const void* X, const void* h0, const void* H, const 
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
-  kern<<<(unsigned)B, 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)H, (const T*)dH, (const T*)wA, (const T*)wB,
-                                      (const T*)bias, (const T*)gi, (const T*)gf, (const T*)Sd, (T*)pA, (T*)pB, (T*)pb,
-                                      (T*)dgi, (T*)dgf, (T*)dh0, (T*)dX, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
-                                      (int)B, gsb, gst, gsn, (const T*)dlogits, (const T*)head_w, (int)NC, (const T*)dY);
+  kern<<<(unsigned)a.B, 1024, lds, a.st>>>((const T*)a.X, (const T*)a.h0, (const T*)a.H, (const T*)a.dH, (const T*)a.wA, (const T*)a.wB,
+                                          (const T*)a.bias, (const T*)a.gi, (const T*)a.gf, (const T*)a.Sd, (T*)a.pA, (T*)a.pB, (T*)a.pb,
+                                          (T*)a.dgi, (T*)a.dgf, (T*)a.dh0, (T*)a.dX, (int)a.T, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
+                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.dlogits, (const T*)a.head_w, (int)a.NC, (const T*)a.dY);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
+}
+
+// The one place that picks the BPTT instantiation: <T, GATED, DX> from the dtype, gi != nullptr and dX != nullptr here, MAXW in the launcher.
+static int dense_bwd_run(int dtype, const DenseBwdArgs& a) {
+  const bool f32 = dtype == GCRNN_F32, gated = a.gi != nullptr;
+  if (!a.dX) {
+    if (f32) return gated ? dense_bwd_launch<float, true, false>(a) : dense_bwd_launch<float, false, false>(a);
+    return gated ? dense_bwd_launch<double, true, false>(a) : dense_bwd_launch<double, false, false>(a);
+  }
+  if (f32) return gated ? dense_bwd_launch<float, true, true>(a) : dense_bwd_launch<float, false, true>(a);
+  return gated ? dense_bwd_launch<double, true, true>(a) : dense_bwd_launch<double, false, true>(a);
 }
 
 extern "C" int gcrnn_small_dense_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH,
@@ -684,17 +724,13 @@ extern "C" int gcrnn_small_dense_backward(int dtype, const void* X, const void* 
                                           int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
                                           int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, void* stream) {
   if (!X || !h0 || !H || !dH || !wA || !wB || !Sdense || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
-  if (B <= 0 || T <= 0 || B > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
+  if (int s = dense_shared_status(gi, gf, true, dgi, dgf, false, dtype)) return s;
+  if (!dense_bt_ok(B, T)) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, 1, gi != nullptr)) return GCRNN_ERR_UNSUPPORTED;
-  hipStream_t st = as_stream(stream);
-#define GCRNN_DENSE_BWD_ARGS X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, nullptr, B, T, N, G, F, Kin, Kst, \
-                             gate_stride_b, gate_stride_t, gate_stride_n, st
-  if (dtype == GCRNN_F32)
-    return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);
-  return gi ? dense_bwd_launch<double, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, false>(GCRNN_DENSE_BWD_ARGS);
-#undef GCRNN_DENSE_BWD_ARGS
+  const DenseBwdArgs a{.X = X, .h0 = h0, .H = H, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .pA = pA, .pB = pB,
+                       .pb = pb, .dgi = dgi, .dgf = dgf, .dh0 = dh0, .dX = nullptr, .B = B, .T = T, .N = N, .G = G, .F = F, .Kin = Kin,
+                       .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n, .st = as_stream(stream), .dH = dH};
+  return dense_bwd_run(dtype, a);
 }
 
 extern "C" int gcrnn_small_dense_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH,
@@ -704,18 +740,13 @@ extern "C" int gcrnn_small_dense_backward_dx(int dtype, const void* X, const voi
                                              int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n,
                                              void* stream) {
   if (!X || !h0 || !H || !dH || !wA || !wB || !Sdense || !pA || !pB || !pb || !dX) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
-  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
-  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (int s = dense_shared_status(gi, gf, true, dgi, dgf, true, dtype)) return s;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gi != nullptr)) return GCRNN_ERR_UNSUPPORTED;
-  hipStream_t st = as_stream(stream);
-#define GCRNN_DENSE_BWD_ARGS X, h0, H, dH, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
-                             gate_stride_b, gate_stride_t, gate_stride_n, st
-  if (dtype == GCRNN_F32)
-    return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
-  return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
-#undef GCRNN_DENSE_BWD_ARGS
+  const DenseBwdArgs a{.X = X, .h0 = h0, .H = H, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .pA = pA, .pB = pB,
+                       .pb = pb, .dgi = dgi, .dgf = dgf, .dh0 = dh0, .dX = dX, .B = B, .T = T, .N = N, .G = G, .F = F, .Kin = Kin,
+                       .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n, .st = as_stream(stream), .dH = dH};
+  return dense_bwd_run(dtype, a);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -736,22 +767,20 @@ extern "C" int gcrnn_small_dense_forward_head(int dtype, const void* X, const vo
                                               int64_t gate_stride_t, int64_t gate_stride_n, int64_t C, int store_states,
                                               void* stream) {
   if (!X || !h0 || !wA || !wB || !Sdense) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
   if ((head_w == nullptr) != (logits == nullptr) || (!head_w && head_b)) return GCRNN_ERR_NULL_POINTER;
-  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (int s = dense_shared_status(gi, gf, false, nullptr, nullptr, true, dtype)) return s;
   if (store_states != GCRNN_SMALL_STATES_ALL && store_states != GCRNN_SMALL_STATES_LAST && store_states != GCRNN_SMALL_STATES_NONE)
     return GCRNN_ERR_BAD_SHAPE;
   if (store_states == GCRNN_SMALL_STATES_NONE ? !head_w : !H) return GCRNN_ERR_NULL_POINTER;      // a launch with nothing to write / no H
-  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
   if (head_w ? C <= 0 : C != 0) return GCRNN_ERR_BAD_SHAPE;
   if (head_w ? !gcrnn_small_dense_head_supported(dtype, N, G, F, Kin, Kst, C, 0, gi != nullptr, 0)
              : !gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, 0, gi != nullptr))
     return GCRNN_ERR_UNSUPPORTED;
-  if (dtype == GCRNN_F32)
-    return dense_fwd_launch<float>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
-                                   gate_stride_n, as_stream(stream), head_w, head_b, logits, C, store_states);
-  return dense_fwd_launch<double>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
-                                  gate_stride_n, as_stream(stream), head_w, head_b, logits, C, store_states);
+  const DenseFwdArgs a{.X = X, .h0 = h0, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .H = H, .B = B, .T = T, .N = N,
+                       .G = G, .F = F, .Kin = Kin, .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n,
+                       .st = as_stream(stream), .head_w = head_w, .head_b = head_b, .out = logits, .NC = C, .store = store_states};
+  return dense_fwd_run(dtype, a, head_w || store_states != GCRNN_SMALL_STATES_ALL ? FWD_LAST : FWD_PLAIN);   // else the plain recurrence
 }
 
 extern "C" int gcrnn_small_dense_backward_head(int dtype, const void* X, const void* h0, const void* H, const void* dlogits,
@@ -761,21 +790,14 @@ extern "C" int gcrnn_small_dense_backward_head(int dtype, const void* X, const v
                                                int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
                                                int64_t gate_stride_t, int64_t gate_stride_n, int64_t C, void* stream) {
   if (!X || !h0 || !H || !dlogits || !head_w || !wA || !wB || !Sdense || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
-  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
-  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0 || C <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (int s = dense_shared_status(gi, gf, true, dgi, dgf, true, dtype)) return s;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0 || C <= 0) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_head_supported(dtype, N, G, F, Kin, Kst, C, 1, gi != nullptr, dX != nullptr)) return GCRNN_ERR_UNSUPPORTED;
-  hipStream_t st = as_stream(stream);
-#define GCRNN_DENSE_BWD_ARGS X, h0, H, nullptr, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
-                             gate_stride_b, gate_stride_t, gate_stride_n, st, dlogits, head_w, C
-  if (dtype == GCRNN_F32) {
-    if (dX) return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
-    return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);
-  }
-  if (dX) return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
-  return gi ? dense_bwd_launch<double, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, false>(GCRNN_DENSE_BWD_ARGS);
-#undef GCRNN_DENSE_BWD_ARGS
+  const DenseBwdArgs a{.X = X, .h0 = h0, .H = H, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .pA = pA, .pB = pB,
+                       .pb = pb, .dgi = dgi, .dgf = dgf, .dh0 = dh0, .dX = dX, .B = B, .T = T, .N = N, .G = G, .F = F, .Kin = Kin,
+                       .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n, .st = as_stream(stream),
+                       .dlogits = dlogits, .head_w = head_w, .NC = C};
+  return dense_bwd_run(dtype, a);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -800,20 +822,18 @@ extern "C" int gcrnn_small_dense_forward_node_head(int dtype, const void* X, con
                                                    int64_t gate_stride_t, int64_t gate_stride_n, int64_t O, int store_states,
                                                    void* stream) {
   if (!X || !h0 || !wA || !wB || !Sdense || !node_w || !Y) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (int s = dense_shared_status(gi, gf, false, nullptr, nullptr, true, dtype)) return s;
   if (store_states != GCRNN_SMALL_STATES_ALL && store_states != GCRNN_SMALL_STATES_LAST && store_states != GCRNN_SMALL_STATES_NONE)
     return GCRNN_ERR_BAD_SHAPE;
   if (store_states != GCRNN_SMALL_STATES_NONE && !H) return GCRNN_ERR_NULL_POINTER;
-  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
   if (O <= 0 || O > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_node_head_supported(dtype, N, G, F, Kin, Kst, O, 0, gi != nullptr, 0)) return GCRNN_ERR_UNSUPPORTED;
   // the training forward stores the states of the forward-only image; its backward is asked separately
-  if (dtype == GCRNN_F32)
-    return dense_fwd_launch<float>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
-                                   gate_stride_n, as_stream(stream), node_w, node_b, Y, O, store_states, true);
-  return dense_fwd_launch<double>(X, h0, wA, wB, bias, gi, gf, Sdense, H, B, T, N, G, F, Kin, Kst, gate_stride_b, gate_stride_t,
-                                  gate_stride_n, as_stream(stream), node_w, node_b, Y, O, store_states, true);
+  const DenseFwdArgs a{.X = X, .h0 = h0, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .H = H, .B = B, .T = T, .N = N,
+                       .G = G, .F = F, .Kin = Kin, .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n,
+                       .st = as_stream(stream), .head_w = node_w, .head_b = node_b, .out = Y, .NC = O, .store = store_states};
+  return dense_fwd_run(dtype, a, FWD_NODE);
 }
 
 extern "C" int gcrnn_small_dense_backward_node_head(int dtype, const void* X, const void* h0, const void* H, const void* dY,
@@ -823,20 +843,13 @@ extern "C" int gcrnn_small_dense_backward_node_head(int dtype, const void* X, co
                                                     int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
                                                     int64_t gate_stride_t, int64_t gate_stride_n, int64_t O, void* stream) {
   if (!X || !h0 || !H || !dY || !node_w || !wA || !wB || !Sdense || !pA || !pB || !pb) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
-  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
-  if (B <= 0 || T <= 0 || B > 2147483647LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (int s = dense_shared_status(gi, gf, true, dgi, dgf, true, dtype)) return s;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
   if (O <= 0 || O > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return GCRNN_ERR_BAD_SHAPE;
   if (!gcrnn_small_dense_node_head_supported(dtype, N, G, F, Kin, Kst, O, 1, gi != nullptr, dX != nullptr)) return GCRNN_ERR_UNSUPPORTED;
-  hipStream_t st = as_stream(stream);
-#define GCRNN_DENSE_BWD_ARGS X, h0, H, nullptr, wA, wB, bias, gi, gf, Sdense, pA, pB, pb, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, \
-                             gate_stride_b, gate_stride_t, gate_stride_n, st, nullptr, node_w, O, dY
-  if (dtype == GCRNN_F32) {
-    if (dX) return gi ? dense_bwd_launch<float, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, true>(GCRNN_DENSE_BWD_ARGS);
-    return gi ? dense_bwd_launch<float, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<float, false, false>(GCRNN_DENSE_BWD_ARGS);
-  }
-  if (dX) return gi ? dense_bwd_launch<double, true, true>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, true>(GCRNN_DENSE_BWD_ARGS);
-  return gi ? dense_bwd_launch<double, true, false>(GCRNN_DENSE_BWD_ARGS) : dense_bwd_launch<double, false, false>(GCRNN_DENSE_BWD_ARGS);
-#undef GCRNN_DENSE_BWD_ARGS
+  const DenseBwdArgs a{.X = X, .h0 = h0, .H = H, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .pA = pA, .pB = pB,
+                       .pb = pb, .dgi = dgi, .dgf = dgf, .dh0 = dh0, .dX = dX, .B = B, .T = T, .N = N, .G = G, .F = F, .Kin = Kin,
+                       .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n, .st = as_stream(stream), .dY = dY,
+                       .head_w = node_w, .NC = O};
+  return dense_bwd_run(dtype, a);
 }

@@ -2990,6 +2990,45 @@ def _gate_strides(g, B, T, N):
 SMALL_STATES_ALL, SMALL_STATES_LAST, SMALL_STATES_NONE = 0, 1, 2      # gcrnn.h: GCRNN_SMALL_STATES_*
 
 
+def _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, head=None):
+    """The one forward launch of the matrix-core family: the recurrence, the states `store` asks for and the output of `head`. head: None,
+    ('last', head_w [C][F N], head_b [C] or None) -- the read-out on the last state, logits [B][C] -- or ('node', node_w [O][F], node_b [O] or
+    None) -- the per-node head on every state, Y [B][T][O][N]. Returns (H or None, logits / Y or None). Entry point: no head and every state
+    gcrnn_small_dense_forward; no head and the last state gcrnn_small_dense_forward_head without a read-out; 'last' the same entry with
+    one; 'node' gcrnn_small_dense_forward_node_head. Every operand stays a local of this frame up to the launch (_small_dense_bptt)."""
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    dt, dev = X.dtype, X.device
+    kind, hw, hb = head if head is not None else (None, None, None)
+    assert head is not None or store != SMALL_STATES_NONE
+    H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
+    out, NC = None, 0
+    if head is not None:
+        NC = hw.shape[0]
+        assert tuple(hw.shape) == ((NC, F * N) if kind == 'last' else (NC, F)) and hw.dtype == dt
+        assert hb is None or (hb.dtype == dt and hb.numel() == NC)
+        out = torch.empty((B, NC) if kind == 'last' else (B, T, NC, N), dtype=dt, device=dev)
+        hw = hw.detach().contiguous()
+        hb = hb.detach().contiguous() if hb is not None else None
+    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+    if gi is not None:
+        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
+    Xc, h0c, wAc, wBc = X.detach().contiguous(), h0.detach().contiguous(), wA.detach().contiguous(), wB.detach().contiguous()
+    Sd = graph.dense(dt)
+    gs = _gate_strides(gi, B, T, N)
+    assert gs == _gate_strides(gf, B, T, N)
+    args = (dtype_code(dt), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(Sd))
+    dims = (B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2])
+    if head is None and store == SMALL_STATES_ALL:
+        name = 'small_dense_forward'
+        args += (_p(H),) + dims
+    else:
+        name = 'small_dense_forward_node_head' if kind == 'node' else 'small_dense_forward_head'
+        args += (_p(hw), _p(hb), _p(H), _p(out)) + dims + (NC, store)
+    check(getattr(lib, 'gcrnn_' + name)(*args, _stream()), name)
+    return H, out
+
+
 def small_cell_forward(X, h0, wA, wB, bias, graph, gi=None, gf=None, last_only=False):
     """Whole recurrence in one launch, one workgroup per sequence (small graphs). X: B x T x G x N, h0: B x F x N
     (user layout, fp32 / fp64) -> H: B x T x F x N. gi / gf: gates of the input / state filter or None: [T][B] scalars per
@@ -2999,26 +3038,13 @@ def small_cell_forward(X, h0, wA, wB, bias, graph, gi=None, gf=None, last_only=F
     require_device(X, h0, wA, wB, bias)
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    if small_dense_supported(N, G, F, Kin, Kst, X.dtype, backward=False, gated=gi is not None):
+        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_LAST if last_only else SMALL_STATES_ALL)[0]
     csr = graph.fwd[0]
     bvec = bias.detach().contiguous().view(-1) if bias is not None else None
     if gi is not None:
         gi, gf = gi.to(X.dtype).contiguous(), gf.to(X.dtype).contiguous()
     Xc, h0c, wAc, wBc, vals = X.contiguous(), h0.contiguous(), wA.contiguous(), wB.contiguous(), csr.val(X.dtype)
-    if small_dense_supported(N, G, F, Kin, Kst, X.dtype, backward=False, gated=gi is not None):
-        Sd = graph.dense(X.dtype)
-        gs = _gate_strides(gi, B, T, N)
-        assert gs == _gate_strides(gf, B, T, N)
-        if last_only:
-            H = torch.empty((B, 1, F, N), dtype=X.dtype, device=X.device)
-            check(lib.gcrnn_small_dense_forward_head(dtype_code(X.dtype), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf),
-                                                     _p(Sd), None, None, _p(H), None, B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2],
-                                                     0, SMALL_STATES_LAST, _stream()), 'small_dense_forward_head')
-            return H
-        H = torch.empty((B, T, F, N), dtype=X.dtype, device=X.device)
-        check(lib.gcrnn_small_dense_forward(dtype_code(X.dtype), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf),
-                                            _p(Sd), _p(H), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], _stream()),
-              'small_dense_forward')
-        return H
     assert gi is None or gi.dim() == 2, 'per-node gates need the matrix-core kernels (small_dense_supported)'
     H = torch.empty((B, T, F, N), dtype=X.dtype, device=X.device)
     check(lib.gcrnn_small_forward(dtype_code(X.dtype), _p(Xc), _p(h0c), _p(wAc),
@@ -3067,61 +3093,82 @@ class _SmallCell(torch.autograd.Function):
         dt, dev = X.dtype, X.device
         fwd, adj = ctx.graph.fwd[0], ctx.graph.adj[0]
         dense = small_dense_supported(N, G, F, Kin, Kst, dt, backward=True, gated=gi is not None)
-        pA = torch.empty((B, 1 if dense else 2, F, Kin, G), dtype=dt, device=dev)
-        pB = torch.empty((B, 1 if dense else 2, F, Kst, F), dtype=dt, device=dev)
+        scalar_gates = gi is not None and gi.dim() == 2
+        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_dx and not small_input_grad_supported(N, fwd.nnz, G, F, Kin, Kst, dt, ctx.graph.E, gated=gi is not None,
+                                                      node_gates=gi is not None and not scalar_gates):
+            raise GcrnnError('small_cell_train: no gradient for X at this shape (small_input_grad_supported)')
+        if dense:
+            return _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dH', dH.contiguous(), None)) + (None,)
+        # the gather family: two slots per sequence, gate gradients [T][B] straight from the kernel
+        pA = torch.empty((B, 2, F, Kin, G), dtype=dt, device=dev)
+        pB = torch.empty((B, 2, F, Kst, F), dtype=dt, device=dev)
         pb = torch.empty((B, F), dtype=dt, device=dev)
         dgi = dgf = None
-        scalar_gates = gi is not None and gi.dim() == 2
         if gi is not None:
-            assert dense or scalar_gates, 'per-node gates need the matrix-core kernels (small_dense_supported)'
+            assert scalar_gates, 'per-node gates need the matrix-core kernels (small_dense_supported)'
             gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
-            shape = (B, T, N) if dense else (T, B)
-            dgi = torch.empty(shape, dtype=dt, device=dev)
-            dgf = torch.empty(shape, dtype=dt, device=dev)
-        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
-        dX = None
-        if ctx.needs_input_grad[0]:
-            if not small_input_grad_supported(N, fwd.nnz, G, F, Kin, Kst, dt, ctx.graph.E, gated=gi is not None,
-                                              node_gates=gi is not None and not scalar_gates):
-                raise GcrnnError('small_cell_train: no gradient for X at this shape (small_input_grad_supported)')
-            dX = torch.empty_like(X)
+            dgi = torch.empty((T, B), dtype=dt, device=dev)
+            dgf = torch.empty((T, B), dtype=dt, device=dev)
+        dh0 = torch.empty_like(h0) if want_dh0 else None
+        dX = torch.empty_like(X) if want_dx else None
         bvec = bias.detach().contiguous().view(-1) if bias is not None else None
-        # every operand is a named local: a temporary (dH.contiguous(), a first-use adj.val(dt)) would be released --
-        # and its block handed to the next allocation -- before the launch
+        # every operand is a named local up to the launch (_small_dense_bptt): dH.contiguous(), a first-use adj.val(dt)
         dHc, wAc, wBc, fval, aval = dH.contiguous(), wA.contiguous(), wB.contiguous(), fwd.val(dt), adj.val(dt)
-        if dense and dX is not None:
-            Sd = ctx.graph.dense(dt)
-            gs = _gate_strides(gi, B, T, N)
-            check(lib.gcrnn_small_dense_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
-                                                    _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0),
-                                                    _p(dX), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], _stream()),
-                  'small_dense_backward_dx')
-            if scalar_gates:
-                dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
-        elif dense:
-            Sd = ctx.graph.dense(dt)
-            gs = _gate_strides(gi, B, T, N)
-            check(lib.gcrnn_small_dense_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
-                                                 _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0),
-                                                 B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], _stream()), 'small_dense_backward')
-            if scalar_gates:                                  # a scalar gate collects the gradients of all its nodes
-                dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
-        elif dX is not None:
-            check(lib.gcrnn_small_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc),
-                                              _p(wBc), _p(bvec), _p(gi), _p(gf), _p(fwd.rowptr), _p(fwd.col),
-                                              _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval), _p(pA), _p(pB), _p(pb),
-                                              _p(dgi), _p(dgf), _p(dh0), _p(dX), B, T, N, G, F, Kin, Kst, fwd.nnz, _stream()),
-                  'small_backward_dx')
-        else:
-            check(lib.gcrnn_small_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc),
-                                           _p(wBc), _p(bvec), _p(gi), _p(gf), _p(fwd.rowptr), _p(fwd.col),
-                                           _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval), _p(pA), _p(pB), _p(pb),
-                                           _p(dgi), _p(dgf), _p(dh0), B, T, N, G, F, Kin, Kst, fwd.nnz, _stream()),
-                  'small_backward')
+        name = 'small_backward_dx' if want_dx else 'small_backward'
+        args = (dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(fwd.rowptr), _p(fwd.col),
+                _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0))
+        check(getattr(lib, 'gcrnn_' + name)(*args, *((_p(dX),) if want_dx else ()), B, T, N, G, F, Kin, Kst, fwd.nnz, _stream()), name)
         dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)
         dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
         db = pb.sum(dim=0).view(F, 1) if bias is not None else None
         return dX, dh0, dwA, dwB, db, dgi, dgf, None
+
+
+def _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, graph, want_dx, want_dh0, seed):
+    """The one BPTT launch of the matrix-core family and its reductions, from the tensors the forward saved. seed: the upstream gradient
+    (kind, gradient, head weight), each contiguous: ('dH', dH [B][T][F][N], None), ('dlogits', dlogits [B][C], head_w [C][F N]) -- the
+    read-out on the last state -- or ('dY', dY [B][T][O][N], node_w [O][F]) -- the per-node head; for the last two the kernel forms dH
+    itself. Entry point: 'dH' gcrnn_small_dense_backward, or gcrnn_small_dense_backward_dx with want_dx; 'dlogits'
+    gcrnn_small_dense_backward_head and 'dY' gcrnn_small_dense_backward_node_head, either with dX or NULL. The caller has asked whether the
+    shape has a dx variant. Returns (dX, dh0, dwA, dwB, db, dgi, dgf); the gradients of a head's own parameters are the caller's.
+
+    Every operand is a named local of this frame up to the launch: a temporary (wA.contiguous(), a first-use graph.dense(dt)) would be
+    released -- and its block handed to the next allocation -- before the launch."""
+    kind, g, hw = seed
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    dt, dev = X.dtype, X.device
+    assert g.is_contiguous() and (hw is None or hw.is_contiguous())
+    pA = torch.empty((B, 1, F, Kin, G), dtype=dt, device=dev)          # one slot per sequence, summed below
+    pB = torch.empty((B, 1, F, Kst, F), dtype=dt, device=dev)
+    pb = torch.empty((B, F), dtype=dt, device=dev)
+    dgi = dgf = None
+    scalar_gates = gi is not None and gi.dim() == 2
+    if gi is not None:
+        gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
+        dgi = torch.empty((B, T, N), dtype=dt, device=dev)
+        dgf = torch.empty((B, T, N), dtype=dt, device=dev)
+    dh0 = torch.empty_like(h0) if want_dh0 else None
+    dX = torch.empty_like(X) if want_dx else None
+    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+    wAc, wBc, Sd = wA.contiguous(), wB.contiguous(), graph.dense(dt)
+    gs = _gate_strides(gi, B, T, N)
+    cell = (_p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0))
+    dims = (B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2])
+    if kind == 'dH':
+        name = 'small_dense_backward_dx' if want_dx else 'small_dense_backward'
+        args = cell + ((_p(dX),) if want_dx else ()) + dims
+    else:
+        name = 'small_dense_backward_head' if kind == 'dlogits' else 'small_dense_backward_node_head'
+        args = (_p(hw),) + cell + (_p(dX),) + dims + (hw.shape[0],)
+    check(getattr(lib, 'gcrnn_' + name)(dtype_code(dt), _p(X), _p(h0), _p(H), _p(g), *args, _stream()), name)
+    if scalar_gates:                                      # a scalar gate collects the gradients of all its nodes
+        dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
+    dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)
+    dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
+    db = pb.sum(dim=0).view(F, 1) if bias is not None else None
+    return dX, dh0, dwA, dwB, db, dgi, dgf
 
 
 def small_cell_train(X, h0, wA, wB, bias, graph, gi=None, gf=None):
@@ -3139,27 +3186,8 @@ def small_head_supported(N, G, F, Kin, Kst, C, dtype, backward, gated, dx=False)
 
 
 def _small_head_forward(X, h0, wA, wB, bias, graph, head_w, head_b, gi, gf, store):
-    """One launch: the recurrence, the states `store` asks for and logits [B][C]. Returns (H or None, logits)."""
-    B, T, G, N = X.shape
-    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
-    C = head_w.shape[0]
-    dt, dev = X.dtype, X.device
-    assert tuple(head_w.shape) == (C, F * N) and head_w.dtype == dt and (head_b is None or (head_b.dtype == dt and head_b.numel() == C))
-    H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
-    logits = torch.empty((B, C), dtype=dt, device=dev)
-    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
-    if gi is not None:
-        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
-    Xc, h0c, wAc, wBc = X.detach().contiguous(), h0.detach().contiguous(), wA.detach().contiguous(), wB.detach().contiguous()
-    hw = head_w.detach().contiguous()
-    hb = head_b.detach().contiguous() if head_b is not None else None
-    Sd = graph.dense(dt)
-    gs = _gate_strides(gi, B, T, N)
-    assert gs == _gate_strides(gf, B, T, N)
-    check(lib.gcrnn_small_dense_forward_head(dtype_code(dt), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(Sd),
-                                             _p(hw), _p(hb), _p(H), _p(logits), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], C,
-                                             store, _stream()), 'small_dense_forward_head')
-    return H, logits
+    """_small_dense_forward with the read-out on the last state: (H or None, logits [B][C])."""
+    return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, ('last', head_w, head_b))
 
 
 class _SmallCellHead(torch.autograd.Function):
@@ -3180,39 +3208,15 @@ class _SmallCellHead(torch.autograd.Function):
         X, h0, H, wA, wB, bias, gi, gf, head_w = ctx.saved_tensors
         B, T, G, N = X.shape
         F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
-        C = head_w.shape[0]
-        dt, dev = X.dtype, X.device
-        pA = torch.empty((B, 1, F, Kin, G), dtype=dt, device=dev)
-        pB = torch.empty((B, 1, F, Kst, F), dtype=dt, device=dev)
-        pb = torch.empty((B, F), dtype=dt, device=dev)
-        dgi = dgf = None
-        scalar_gates = gi is not None and gi.dim() == 2
-        if gi is not None:
-            gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
-            dgi = torch.empty((B, T, N), dtype=dt, device=dev)
-            dgf = torch.empty((B, T, N), dtype=dt, device=dev)
-        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
-        dX = None
-        if ctx.needs_input_grad[0]:
-            if not small_head_supported(N, G, F, Kin, Kst, C, dt, True, gi is not None, dx=True):
-                raise GcrnnError('small_cell_classify: no gradient for X at this shape (small_head_supported with dx)')
-            dX = torch.empty_like(X)
-        bvec = bias.detach().contiguous().view(-1) if bias is not None else None
-        # every operand is a named local up to the launch (see _SmallCell.backward)
-        dlc, hw, wAc, wBc, Sd = dlogits.contiguous(), head_w.detach().contiguous(), wA.contiguous(), wB.contiguous(), ctx.graph.dense(dt)
-        gs = _gate_strides(gi, B, T, N)
-        check(lib.gcrnn_small_dense_backward_head(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dlc), _p(hw), _p(wAc), _p(wBc), _p(bvec),
-                                                  _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0), _p(dX),
-                                                  B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], C, _stream()),
-              'small_dense_backward_head')
-        if scalar_gates:                                  # a scalar gate collects the gradients of all its nodes
-            dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
-        dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)            # the reductions of _SmallCell.backward, shape for shape
-        dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
-        db = pb.sum(dim=0).view(F, 1) if bias is not None else None
+        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_dx and not small_head_supported(N, G, F, Kin, Kst, head_w.shape[0], X.dtype, True, gi is not None, dx=True):
+            raise GcrnnError('small_cell_classify: no gradient for X at this shape (small_head_supported with dx)')
+        dlc = dlogits.contiguous()
+        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0,
+                                  ('dlogits', dlc, head_w.detach().contiguous()))
         dhw = dlc.t().mm(H[:, -1].reshape(B, F * N)) if ctx.needs_input_grad[7] else None
         dhb = dlc.sum(dim=0) if ctx.has_hb and ctx.needs_input_grad[8] else None
-        return dX, dh0, dwA, dwB, db, dgi, dgf, dhw, dhb, None
+        return grads + (dhw, dhb, None)
 
 
 def small_cell_classify(X, h0, wA, wB, bias, graph, head_w, head_b, gi=None, gf=None):
@@ -3223,7 +3227,7 @@ def small_cell_classify(X, h0, wA, wB, bias, graph, head_w, head_b, gi=None, gf=
     require_device(X, h0, wA, wB, bias, head_w)
     operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b)
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
-        return _small_head_forward(X, h0, wA, wB, bias, graph, head_w, head_b, gi, gf, SMALL_STATES_NONE)[1]
+        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('last', head_w, head_b))[1]
     return _SmallCellHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph)
 
 
@@ -3241,27 +3245,8 @@ def small_node_head_supported(N, G, F, Kin, Kst, O, dtype, backward, gated, dx=F
 
 
 def _small_node_head_forward(X, h0, wA, wB, bias, graph, node_w, node_b, gi, gf, store):
-    """One launch: the recurrence, the states `store` asks for and Y [B][T][O][N]. Returns (H or None, Y)."""
-    B, T, G, N = X.shape
-    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
-    O = node_w.shape[0]
-    dt, dev = X.dtype, X.device
-    assert tuple(node_w.shape) == (O, F) and node_w.dtype == dt and (node_b is None or (node_b.dtype == dt and node_b.numel() == O))
-    H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
-    Y = torch.empty((B, T, O, N), dtype=dt, device=dev)
-    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
-    if gi is not None:
-        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
-    Xc, h0c, wAc, wBc = X.detach().contiguous(), h0.detach().contiguous(), wA.detach().contiguous(), wB.detach().contiguous()
-    nw = node_w.detach().contiguous()
-    nb = node_b.detach().contiguous() if node_b is not None else None
-    Sd = graph.dense(dt)
-    gs = _gate_strides(gi, B, T, N)
-    assert gs == _gate_strides(gf, B, T, N)
-    check(lib.gcrnn_small_dense_forward_node_head(dtype_code(dt), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(gi), _p(gf), _p(Sd),
-                                                  _p(nw), _p(nb), _p(H), _p(Y), B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], O,
-                                                  store, _stream()), 'small_dense_forward_node_head')
-    return H, Y
+    """_small_dense_forward with the per-node head on every state: (H or None, Y [B][T][O][N])."""
+    return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, ('node', node_w, node_b))
 
 
 class _SmallCellNodeHead(torch.autograd.Function):
@@ -3285,34 +3270,11 @@ class _SmallCellNodeHead(torch.autograd.Function):
         F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
         O = node_w.shape[0]
         dt, dev = X.dtype, X.device
-        pA = torch.empty((B, 1, F, Kin, G), dtype=dt, device=dev)
-        pB = torch.empty((B, 1, F, Kst, F), dtype=dt, device=dev)
-        pb = torch.empty((B, F), dtype=dt, device=dev)
-        dgi = dgf = None
-        scalar_gates = gi is not None and gi.dim() == 2
-        if gi is not None:
-            gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
-            dgi = torch.empty((B, T, N), dtype=dt, device=dev)
-            dgf = torch.empty((B, T, N), dtype=dt, device=dev)
-        dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
-        dX = None
-        if ctx.needs_input_grad[0]:
-            if not small_node_head_supported(N, G, F, Kin, Kst, O, dt, True, gi is not None, dx=True):
-                raise GcrnnError('small_cell_regress: no gradient for X at this shape (small_node_head_supported with dx)')
-            dX = torch.empty_like(X)
-        bvec = bias.detach().contiguous().view(-1) if bias is not None else None
-        # every operand is a named local up to the launch (see _SmallCell.backward)
-        dYc, nw, wAc, wBc, Sd = dY.contiguous(), node_w.detach().contiguous(), wA.contiguous(), wB.contiguous(), ctx.graph.dense(dt)
-        gs = _gate_strides(gi, B, T, N)
-        check(lib.gcrnn_small_dense_backward_node_head(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dYc), _p(nw), _p(wAc), _p(wBc), _p(bvec),
-                                                       _p(gi), _p(gf), _p(Sd), _p(pA), _p(pB), _p(pb), _p(dgi), _p(dgf), _p(dh0), _p(dX),
-                                                       B, T, N, G, F, Kin, Kst, gs[0], gs[1], gs[2], O, _stream()),
-              'small_dense_backward_node_head')
-        if scalar_gates:                                  # a scalar gate collects the gradients of all its nodes
-            dgi, dgf = dgi.sum(dim=2).t(), dgf.sum(dim=2).t()
-        dwA = pA.sum(dim=(0, 1)).view(F, 1, Kin, G)            # the reductions of _SmallCell.backward, shape for shape
-        dwB = pB.sum(dim=(0, 1)).view(F, 1, Kst, F)
-        db = pb.sum(dim=0).view(F, 1) if bias is not None else None
+        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_dx and not small_node_head_supported(N, G, F, Kin, Kst, O, dt, True, gi is not None, dx=True):
+            raise GcrnnError('small_cell_regress: no gradient for X at this shape (small_node_head_supported with dx)')
+        dYc, nw = dY.contiguous(), node_w.detach().contiguous()
+        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dY', dYc, nw))
         # d node_w[o][f] = sum_{b,t,n} dY[b][t][o][n] H[b][t][f][n] and d node_b[o] = sum dY: neither makes a [B][T][F][N] temporary
         dnw = dnb = None
         want_nb = ctx.has_nb and ctx.needs_input_grad[8]
@@ -3331,7 +3293,7 @@ class _SmallCellNodeHead(torch.autograd.Function):
             if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B T][O][F] its only temporary
                 dnw = torch.bmm(dYc.view(B * T, O, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
             dnb = dYc.sum(dim=(0, 1, 3)) if want_nb else None
-        return dX, dh0, dwA, dwB, db, dgi, dgf, dnw, dnb, None
+        return grads + (dnw, dnb, None)
 
 
 def small_cell_regress(X, h0, wA, wB, bias, graph, node_w, node_b, gi=None, gf=None):
@@ -3342,7 +3304,7 @@ def small_cell_regress(X, h0, wA, wB, bias, graph, node_w, node_b, gi=None, gf=N
     require_device(X, h0, wA, wB, bias, node_w)
     operands = (X, h0, wA, wB, bias, gi, gf, node_w, node_b)
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
-        return _small_node_head_forward(X, h0, wA, wB, bias, graph, node_w, node_b, gi, gf, SMALL_STATES_NONE)[1]
+        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('node', node_w, node_b))[1]
     return _SmallCellNodeHead.apply(X, h0, wA, wB, bias, gi, gf, node_w, node_b, graph)
 
 
@@ -3386,16 +3348,11 @@ class _SmallTimeGates(torch.autograd.Function):
         plw = torch.empty((B, 2, F * N), dtype=dt, device=dev)
         plb = torch.empty((B, 2), dtype=dt, device=dev)
         pdh0 = torch.empty((B, 2, F, N), dtype=dt, device=dev) if ctx.needs_input_grad[1] else None
-        pdX = None
-        if ctx.needs_input_grad[0]:
-            pdX = torch.empty((B, 2, T, G, N), dtype=dt, device=dev)
-            check(lib.gcrnn_small_gates_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(lw2), _p(Sd),
-                                                    _p(dsum), _p(pA), _p(pB), _p(pb), _p(plw), _p(plb), _p(pdh0), _p(pdX), B, T, N,
-                                                    G, F, Kin, Kst, _stream()), 'small_gates_backward_dx')
-        else:
-            check(lib.gcrnn_small_gates_backward(dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(lw2), _p(Sd),
-                                                 _p(dsum), _p(pA), _p(pB), _p(pb), _p(plw), _p(plb), _p(pdh0), B, T, N, G, F, Kin,
-                                                 Kst, _stream()), 'small_gates_backward')
+        pdX = torch.empty((B, 2, T, G, N), dtype=dt, device=dev) if ctx.needs_input_grad[0] else None
+        name = 'small_gates_backward_dx' if pdX is not None else 'small_gates_backward'
+        args = (dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(lw2), _p(Sd), _p(dsum), _p(pA), _p(pB), _p(pb), _p(plw),
+                _p(plb), _p(pdh0))
+        check(getattr(lib, 'gcrnn_' + name)(*args, *((_p(pdX),) if pdX is not None else ()), B, T, N, G, F, Kin, Kst, _stream()), name)
         return (pdX[:, 0] + pdX[:, 1] if pdX is not None else None, pdh0.sum(dim=1) if pdh0 is not None else None, pA.sum(dim=0), pB.sum(dim=0),
                 pb.sum(dim=0) if bias2 is not None else None, plw.sum(dim=0), plb.sum(dim=0) if ctx.has_lb else None, None)
 
@@ -3527,26 +3484,17 @@ class _SmallEdgeCell(torch.autograd.Function):
         dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
         dX = torch.empty_like(X) if ctx.needs_input_grad[0] else None
         bvec = bias.contiguous().view(-1) if bias is not None else None
-        # every operand is a named local (see _SmallCell.backward)
+        # every operand is a named local (see _small_dense_bptt)
         dHc, wAc, wBc = dH.contiguous(), wA.contiguous(), wB.contiguous()
         wi, ai, wfo, afo = w_in.contiguous(), m_in.contiguous(), w_f.contiguous(), m_f.contiguous()
         fval, aval, tvals = fwd.val(dt), adj.val(dt), _edge_support_values(graph, dt)
-        if dX is not None:
-            check(lib.gcrnn_small_edge_backward_dx(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
-                                                   _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
-                                                   _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
-                                                   _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']),
-                                                   _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB),
-                                                   _p(dgi), _p(dgf), _p(dh0), _p(dX), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs,
-                                                   _stream()), 'small_edge_backward_dx')
-        else:
-            check(lib.gcrnn_small_edge_backward(dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec),
-                                                _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
-                                                _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
-                                                _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']),
-                                                _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB),
-                                                _p(dgi), _p(dgf), _p(dh0), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs, _stream()),
-                  'small_edge_backward')
+        name = 'small_edge_backward_dx' if dX is not None else 'small_edge_backward'
+        args = (dtype_code(dt), _p(X), _p(h0), _p(H), _p(dHc), _p(wAc), _p(wBc), _p(bvec), _p(wi), _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf),
+                _p(fwd.rowptr), _p(fwd.col), _p(fval), _p(adj.rowptr), _p(adj.col), _p(aval),
+                _p(plan['rowptr']), _p(plan['r_edge']), _p(plan['t_rowptr']), _p(plan['t_edge']), _p(tvals), _p(plan['t_pos']),
+                _p(dPre), _p(pwfA), _p(pbfA), _p(pwfB), _p(pbfB), _p(dgi), _p(dgf), _p(dh0))
+        check(getattr(lib, 'gcrnn_' + name)(*args, *((_p(dX),) if dX is not None else ()), B, T, N, G, F, Kin, Kst, fwd.nnz, nnzs, _stream()),
+              name)
         dwA, dbA, dm_in, dw_in = _edge_unfold(pwfA, pbfA, wAc, bias, ai, wi)
         dwB, dbB, dm_f, dw_f = _edge_unfold(pwfB, pbfB, wBc, bias, afo, wfo)
         db = dbA + dbB if bias is not None else None              # one bias, both branches
