@@ -661,6 +661,13 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       taps(K - 1);
       put(std::false_type{});
     };
+    // The seed's tap alone, for the chunk boundaries where it runs beside the user-layout row stores: it reads the operand and the weight
+    // fragments only, so the image's place may still hold the transposed tile.
+    auto seed_taps_beside_rows = [&]() {
+#pragma unroll
+      for (int i = 0; i < STILES; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      taps(K - 1);
+    };
     seed();
 
 #pragma unroll 1
@@ -922,7 +929,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 
       // ---- epilogue: + 2 b, tanh, bf16; lane (r, q) holds features 32 c + 8 q .. + 7 of its node: ONE 16-byte store per tile ------------
       typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4_t;
-      const int lane = lane_now(), q = lane >> 4, tl = wave * 64 + lane;
+      const int lane = lane_now(), q = lane >> 4;
       // VAR bit 2: this workgroup's state scratch (scalar registers, made where it is used)
       auto scratch_rsrc = [&]() {
         return __builtin_amdgcn_make_buffer_rsrc(SCRV ? a.scr + (int64_t)blockIdx.x * ((HS - 1) * (SCR_CH / 2)) : nullptr, 0, SCRV ? (HS - 1) * SCR_CH : 0, 0x00020000);
@@ -1226,21 +1233,62 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         }
         lds_barrier();
         GCRNN_STAMP32(1 + chunk * 24 + 18);
+      }
+      // The next chunk's seed taps beside the row stores (user-layout forward, un-gated, not the step's last chunk -- its seed waits for the
+      // next operand): the tap reads the resident operand, the next chunk's tap K-1 fragments (landed under hop 1's vmcnt(0) + barrier) and
+      // zeroed accumulators (dead since pkd was formed) -- nothing the row stores produce, and only its `put` needs the tile to have been
+      // read. As in a hop, the two waves of a SIMD take the two phases in opposite order: waves 0..3 run the 64 MFMAs while waves 4..7 drain
+      // their rows (LDS reads + stores, the matrix pipe idle), then the other way round. hipcc puts s_waitcnt vmcnt(0) in front of the tap's
+      // MFMAs (it places waits per block, not per path: the block is reachable from the last chunk's operand requests into the same
+      // registers) -- as it did in front of the seed behind the end barrier, where all eight waves sat out the retirement of the row stores.
+      // Now waves 0..3 wait for the chunk's state stores only (issued a tile phase earlier) and waves 4..7 for their own row stores while
+      // waves 0..3 work. K = 2: tap 0 of the next chunk is still landing (its wait is below); the seed reads tap 1. Every wave tapping first,
+      // then storing, measured 3 units more per boundary (end barrier 3.8 -> 9.6, profiles/epilogue_stamps_variants.txt).
+      constexpr bool OVL = USERV && MODE == 0 && !GATED && !SPLIT;
+      const bool ovl = OVL && chunk + 1 < NCH;
+      if (ovl && wave < SWAVES / 2) {
+        seed_taps_beside_rows();
+        GCRNN_STAMP32(1 + chunk * 24 + 21);
+      }
+      if (aux1) {
+        const char* tst = smem;
         const int segs = N >> 3;
         uint16_t* ub = const_cast<uint16_t*>(aux1) + (int64_t)b * ubstride + (int64_t)(chunk * 32) * N;
         const __amdgpu_buffer_rsrc_t rsrc_u = __builtin_amdgcn_make_buffer_rsrc(ub, 0, 32 * N * 2, 0x00020000);
-        for (int idx = tl; idx < 16 * segs; idx += STHREADS) {
-          const int fp = idx / segs, sg = idx - fp * segs;
-          const u32x4_t w0 = *reinterpret_cast<const u32x4_t*>(tst + fp * RS2 + sg * 32);
-          const u32x4_t w1 = *reinterpret_cast<const u32x4_t*>(tst + fp * RS2 + sg * 32 + 16);
-          const u32x4_t ev = {__builtin_amdgcn_perm(w0[1], w0[0], 0x05040100u), __builtin_amdgcn_perm(w0[3], w0[2], 0x05040100u),
-                              __builtin_amdgcn_perm(w1[1], w1[0], 0x05040100u), __builtin_amdgcn_perm(w1[3], w1[2], 0x05040100u)};
-          const u32x4_t od = {__builtin_amdgcn_perm(w0[1], w0[0], 0x07060302u), __builtin_amdgcn_perm(w0[3], w0[2], 0x07060302u),
-                              __builtin_amdgcn_perm(w1[1], w1[0], 0x07060302u), __builtin_amdgcn_perm(w1[3], w1[2], 0x07060302u)};
-          __builtin_amdgcn_raw_buffer_store_b128(ev, rsrc_u, ((2 * fp) * N + sg * 8) * 2, 0, GCRNN_SEQ32_NT_ROWS);
-          __builtin_amdgcn_raw_buffer_store_b128(od, rsrc_u, ((2 * fp + 1) * N + sg * 8) * 2, 0, GCRNN_SEQ32_NT_ROWS);
+        // Static mapping: wave w drains feature-pair rows 2 w and 2 w + 1, a lane the 8-node segments sg = lane and lane + 64 of each (two
+        // sweeps cover segs <= 128) -- no division, one base address with immediate offsets, ALL eight LDS reads of the lane in flight before
+        // the first v_perm (they are inside the tile for every lane: 128 * 32 <= RS2; what lies beyond N nodes is read and never stored), and
+        // every store piece in a register tuple of its own before the first store (gfx950 store-data convention). A
+        // wave-instruction still stores 1 KB of contiguous bytes of one H row.
+        static_assert(SWAVES * 2 == 16 && 128 * 32 <= RS2, "row stores: two feature-pair rows per wave, two sweeps of 64 segments inside a tile row");
+        const int ln = lane_now();
+        const char* rb = tst + (2 * wave) * RS2 + ln * 32;
+        u32x4_t rw[4][2], rv[4][2];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {      // piece p: row 2 w + (p & 1), sweep p >> 1
+          rw[p][0] = *reinterpret_cast<const u32x4_t*>(rb + (p & 1) * RS2 + (p >> 1) * 2048);
+          rw[p][1] = *reinterpret_cast<const u32x4_t*>(rb + (p & 1) * RS2 + (p >> 1) * 2048 + 16);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const u32x4_t w0 = rw[p][0], w1 = rw[p][1];
+          rv[p][0] = u32x4_t{__builtin_amdgcn_perm(w0[1], w0[0], 0x05040100u), __builtin_amdgcn_perm(w0[3], w0[2], 0x05040100u),
+                             __builtin_amdgcn_perm(w1[1], w1[0], 0x05040100u), __builtin_amdgcn_perm(w1[3], w1[2], 0x05040100u)};
+          rv[p][1] = u32x4_t{__builtin_amdgcn_perm(w0[1], w0[0], 0x07060302u), __builtin_amdgcn_perm(w0[3], w0[2], 0x07060302u),
+                             __builtin_amdgcn_perm(w1[1], w1[0], 0x07060302u), __builtin_amdgcn_perm(w1[3], w1[2], 0x07060302u)};
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { asm volatile("" : "+v"(rv[p][0])); asm volatile("" : "+v"(rv[p][1])); }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int fp = 2 * wave + (p & 1), sg = ln + 64 * (p >> 1);
+          if (sg < segs) {
+            __builtin_amdgcn_raw_buffer_store_b128(rv[p][0], rsrc_u, ((2 * fp) * N + sg * 8) * 2, 0, GCRNN_SEQ32_NT_ROWS);
+            __builtin_amdgcn_raw_buffer_store_b128(rv[p][1], rsrc_u, ((2 * fp + 1) * N + sg * 8) * 2, 0, GCRNN_SEQ32_NT_ROWS);
+          }
         }
       }
+      if (ovl && wave >= SWAVES / 2) seed_taps_beside_rows();
       // this chunk's stores have retired (the next step reads some of them back; K = 2: the next chunk's tap 0 has landed), the tile
       // has been read: the image may be seeded again
       if (GCRNN_SEQ32_OPERAND_AT == 2) request_next_operand();
@@ -1253,7 +1301,10 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       else if (GCRNN_SEQ32_END_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       lds_barrier();
       GCRNN_STAMP32(1 + chunk * 24 + 20);
-      if (!SPLIT && chunk + 1 < NCH) seed();
+      if (!SPLIT && chunk + 1 < NCH) {
+        if (ovl) put(std::false_type{});      // (its taps ran beside the row stores)
+        else seed();
+      }
     }  // chunks
   }  // steps
   }  // sequences

@@ -63,8 +63,14 @@ with torch.no_grad():
 torch.cuda.synchronize()
 buf = np.zeros(256 * 96, dtype=np.uint64)
 dll = ctypes.CDLL(lib)
-pinned = os.environ.get('GCRNN_SEQ32P', '1') != '0' and not (chain or gates)      # the un-gated forward runs the hand-allocated-hop kernel (gcrnn_fused_seq32p.h)
-assert (dll.gcrnn_debug_read_seq32p_stamps if pinned else dll.gcrnn_debug_read_seq32_stamps)(buf.ctypes.data_as(ctypes.c_void_p)) == 0
+# which unit ran: sequence-major in and out -> the hand-allocated-hop kernel (gcrnn_fused_seq32p.h) unless GCRNN_SEQ32P=0; the module's call
+# (user layout) -> the state-scratch launch with self-start as issued (gcrnn_fused_seq32s.hip, VAR 7) unless GCRNN_SEQ32_STATE_SCRATCH=0 or
+# GCRNN_SEQ32P=1 select the older forms; the chain and the gate pre-pass -> gcrnn_fused_seq32.hip
+p32 = os.environ.get('GCRNN_SEQ32P')
+pinned = not (chain or gates) and (p32 != '0' if native else (p32 is not None and p32 != '0'))
+scratch = not (chain or gates or native or pinned) and os.environ.get('GCRNN_SEQ32_STATE_SCRATCH', '1') != '0'
+reader = dll.gcrnn_debug_read_seq32p_stamps if pinned else dll.gcrnn_debug_read_seq32s_stamps if scratch else dll.gcrnn_debug_read_seq32_stamps
+assert reader(buf.ctypes.data_as(ctypes.c_void_p)) == 0
 st = buf.reshape(256, 96).astype(np.int64)
 names = {0: 'step start (operand in registers)'}
 for c in range(4 if gates else 2):
@@ -77,12 +83,15 @@ for c in range(4 if gates else 2):
         names[b0 + 4 * (j - 1) + 4] = 'c%d hop %d put + weights dma + pack drain + barrier' % (c, j)
     names[b0 + 17] = 'c%d next operand requests + tanh + state stores' % c
     names[b0 + 18] = 'c%d transposed tile + barrier' % c
+    if (st[:, b0 + 21] > st[:, b0 + 18]).all():      # (the next chunk's seed taps beside the row stores: wave 0 evaluates them first)
+        names[b0 + 21] = 'c%d next seed taps (wave 0; waves 4-7: rows)' % c
     names[b0 + 19] = 'c%d user-layout row stores' % c
     names[b0 + 20] = 'c%d vmcnt(0) + end barrier' % c
 prev = 0
+print('kernel unit: %s' % ('gcrnn_fused_seq32p' if pinned else 'gcrnn_fused_seq32s (state scratch, as issued)' if scratch else 'gcrnn_fused_seq32'))
 print('stamps of step T-3 of the persistent launch (%s), median over 256 workgroups; unit = 100 shader cycles (s_memtime)' % ('time gates, pair pre-pass: first item of a workgroup, X laid out by the caller' if gates else 'BPTT data chain, inline layout of dH' if chain else 'native layout' if native else 'user layout + inline pack'))
 tot = {}
-for s in sorted(names):
+for s in names:      # (insertion order = order in time)
     d = st[:, s] - st[:, prev]
     print('%-52s +%7.2f   (min %.2f max %.2f)   t = %.2f' % (names[s], np.median(d) / 100.0, d.min() / 100.0, d.max() / 100.0, np.median(st[:, s] - st[:, 0]) / 100.0))
     key = names[s].split(' ', 1)[1] if names[s][0] == 'c' else names[s]
