@@ -757,7 +757,8 @@ class GGCRNNCell(nn.Module):
         route = self._small_head_route(X, h0, weight, bias, 'GCRNN_NO_SMALL_HEAD', lambda w: w.shape[1] == self.F * self.N,
                                        self._small_last_state_pays, ops.small_head_supported)
         if route is None:
-            return None
+            return self._small_edge_head(X, h0, weight, bias, 'GCRNN_NO_SMALL_HEAD', lambda w: w.shape[1] == self.F * self.N,
+                                         ops.SMALL_EDGE_HEAD_LAST, ops.small_edge_cell_classify)
         return ops.small_cell_classify(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
 
     def _small_head_route(self, X, h0, weight, bias, off_switch, weight_ok, pays, supported):
@@ -787,6 +788,51 @@ class GGCRNNCell(nn.Module):
         return (backward,) + self._small_gates(X, h0, backward)
 
     @staticmethod
+    def _small_edge_head_pays(X, head_kind):
+        """Where the edge-gated recurrence launches with the head inside them are no slower than the two-module path (the acceptance rule of
+        DESIGN 4.11 / 4.12 on tools/small_edge_head_bench.py's rows): the read-out in fp32 and fp64 and the per-node head in
+        fp32, inference and training step. The per-node head in fp64 fails the rule at T = 20 and T = 200, edge and time+edge, this path /
+        the parent tree in ms: inference 0.655 / 0.651 and 6.258 / 6.181, training step 2.244 / 2.226 and 20.13 / 19.94 (SBM 50, F = 20,
+        K = 5, B = 100) -- the O N threads that form y_t sit on the step's critical path and cost more than the state stores they replace.
+        Those rows are taken off the dispatch here; GCRNN_SMALL_EDGE_HEAD=all takes them all the same (inference memory halves)."""
+        return not (head_kind == ops.SMALL_EDGE_HEAD_NODE and X.dtype == torch.float64)
+
+    def _small_edge_head(self, X, h0, weight, bias, off_switch, weight_ok, head_kind, fn):
+        """classify / regress of an EDGE-gated cell (optionally time-gated too) on a small graph: the head inside the one-launch edge-gated
+        recurrence and its BPTT (ops.small_edge_cell_classify / _regress). Opt-in: GCRNN_SMALL_EDGE_HEAD=1, read at every call
+        (the default keeps the two-module path that existing tests pin; a later change may flip it), takes the rows that pay
+        (_small_edge_head_pays); GCRNN_SMALL_EDGE_HEAD=all takes every supported row. GCRNN_NO_SMALL_EDGE=1 and the head's own off_switch
+        win over it. Returns the head's output, or None to decline: the cell must take _use_small_edge (inference) or
+        _use_small_edge_training (training, with its GCRNN_SMALL_EDGE_DX rule for an X that wants a gradient), the head the tests of
+        _small_head_route, the shape ops.small_edge_head_supported."""
+        mode = os.environ.get('GCRNN_SMALL_EDGE_HEAD')
+        if not mode or os.environ.get(off_switch) or self.spatial_gating != 'edge':
+            return None
+        if mode != 'all' and not self._small_edge_head_pays(X, head_kind):
+            return None
+        if self.graph is None or self._state_padded(X, h0) is not None:
+            return None
+        if weight.dim() != 2 or not weight_ok(weight) or weight.dtype != X.dtype or (bias is not None and bias.dtype != X.dtype):
+            return None
+        head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
+        if self._use_small_edge(X, h0):
+            train = False
+        elif self._use_small_edge_training(X, h0):
+            train = True
+        else:
+            return None
+        backward = train or head_grad
+        if not ops.small_edge_head_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin, self.Kst,
+                                             head_kind, weight.shape[0], X.dtype, backward, self.E):
+            return None
+        assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
+        ops.require_device(X, h0, self.weight_A)
+        gi, gf = self._small_time_gates(X, h0, backward)
+        att_in = (self.input_attention.mixer, self.input_attention.weight)
+        att_f = (self.forget_attention.mixer, self.forget_attention.weight)
+        return fn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, weight, bias, gi, gf)
+
+    @staticmethod
     def _small_node_head_pays(X):
         """Inference with the per-node head inside the matrix-core forward (no state stored) against the all-states launch + node_linear:
         every shape. Measured at the k-step driver's shape (N = 80, F = 20, K = 5, B = 100), this path / the parent tree, ms:
@@ -806,7 +852,8 @@ class GGCRNNCell(nn.Module):
         route = self._small_head_route(X, h0, weight, bias, 'GCRNN_NO_SMALL_NODE_HEAD', lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
                                        self._small_node_head_pays, ops.small_node_head_supported)
         if route is None:
-            return None
+            return self._small_edge_head(X, h0, weight, bias, 'GCRNN_NO_SMALL_NODE_HEAD', lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
+                                         ops.SMALL_EDGE_HEAD_NODE, ops.small_edge_cell_regress)
         return ops.small_cell_regress(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
 
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----

@@ -186,6 +186,9 @@ def _bind(lib):
         'gcrnn_small_edge_backward_supported': (C.c_int, [C.c_int] + [_c_i64] * 7),
         'gcrnn_small_edge_backward': (C.c_int, [C.c_int] + [_c_p] * 33 + [_c_i64] * 9 + [_c_p]),
         'gcrnn_small_edge_backward_dx': (C.c_int, [C.c_int] + [_c_p] * 34 + [_c_i64] * 9 + [_c_p]),
+        'gcrnn_small_edge_head_supported': (C.c_int, [C.c_int] + [_c_i64] * 7 + [C.c_int, _c_i64, C.c_int]),
+        'gcrnn_small_edge_forward_head': (C.c_int, [C.c_int] + [_c_p] * 24 + [_c_i64] * 10 + [C.c_int, C.c_int, _c_p]),
+        'gcrnn_small_edge_backward_head': (C.c_int, [C.c_int] + [_c_p] * 35 + [_c_i64] * 10 + [C.c_int, _c_p]),
         'gcrnn_node_linear_blocks': (_c_i64, [_c_i64, _c_i64]),
         'gcrnn_node_linear_forward': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
         'gcrnn_node_linear_backward': (C.c_int, [C.c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),

@@ -16,6 +16,11 @@
 // The input branch does not depend on the state. XP = true evaluates it for every (b, t) in one launch of B * T workgroups and
 // writes Ya[b][t] = gi_t * y_a; XP = false walks t = 0 .. T-1 with h_t = tanh(Ya[b][t] + gf_t * y_b). Two launches per forward,
 // whatever T is.
+//
+// HEAD (recurrence launch only) puts the model's output head behind the state while it sits in LDS (z_0 = h_t):
+//   SE_HEAD_LAST  logits[b][c] = head_w[c] . vec(h_T) + head_b[c]        (classification read-out, one wave per class, behind the loop)
+//   SE_HEAD_NODE  y_t[o][n] = node_b[o] + sum_f node_w[o][f] h_t[f][n]   (regression head on every state, one thread per (o, n))
+// and `store` (GCRNN_SMALL_STATES_*) says which states still go to H. The stored states keep the bits of HEAD = NONE.
 #include "gcrnn_common.h"
 
 namespace {
@@ -30,10 +35,26 @@ template <> __device__ __forceinline__ double se_exp<double>(double v) { return 
 constexpr int SE_THREADS = 1024;
 constexpr int SE_PASSES = 4;             // (F + 2) * N <= SE_PASSES * SE_THREADS is checked on the host
 constexpr int SE_ROW_LANES = 8;          // lanes that share one support row in the row pass
+constexpr int SE_HEAD_NONE = 0, SE_HEAD_LAST = 1, SE_HEAD_NODE = 2;
+
+// y[o][n] of the per-node head from the state in z_0: from the bias, f ascending (node_linear_fwd_kernel's order). The O N threads at the END
+// of the workgroup: the hop and tap passes load the low thread indices twice when F N > SE_THREADS.
+template <typename T>
+__device__ __forceinline__ void se_node_head(const T* __restrict__ z, const T* __restrict__ hwl, T* __restrict__ y, int tid, int N, int F,
+                                             int O) {
+  const int idx = tid - (SE_THREADS - O * N);
+  if (idx >= 0) {
+    const int o = idx / N, n = idx - o * N;
+    const T* wr = hwl + o * F;
+    T acc = hwl[O * F + o];
+    for (int f = 0; f < F; ++f) acc += wr[f] * z[f * N + n];
+    y[idx] = acc;
+  }
+}
 
 }  // namespace
 
-template <typename T, bool XP>
+template <typename T, bool XP, int HEAD = SE_HEAD_NONE>
 __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
     const T* __restrict__ U,          // XP: X [B][Tn][C][N]        else: h0 [B][C][N]  (C = F)
     const T* __restrict__ w,          // [F][K][C] filter taps
@@ -45,8 +66,12 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
     const int32_t* __restrict__ s_rowptr, const int2* __restrict__ r_edge,                                // support rows: {n, .}
     const int32_t* __restrict__ t_rowptr, const int2* __restrict__ t_edge, const T* __restrict__ t_val,   // support columns: {m, .}, (S + I)[m][n]
     T* __restrict__ Ya,               // [B][Tn][F][N]              XP: written, else: read
-    T* __restrict__ H,                // [B][Tn][F][N] or, last_only, [B][1][F][N]   (not XP)
-    int Tn, int N, int C, int F, int K, int nnz, int nnzs, int B, int last_only) {
+    T* __restrict__ H,                // [B][Tn][F][N] or, last_only, [B][1][F][N]   (not XP); with a head: by `last_only` = GCRNN_SMALL_STATES_*
+    const T* __restrict__ head_w,     // HEAD_LAST: [NC][F N]       HEAD_NODE: [NC][F]
+    const T* __restrict__ head_b,     // [NC] or null
+    T* __restrict__ Y,                // HEAD_LAST: logits [B][NC]  HEAD_NODE: [B][Tn][NC][N]
+    int Tn, int N, int C, int F, int K, int nnz, int nnzs, int B, int last_only, int NC) {
+  static_assert(!XP || HEAD == SE_HEAD_NONE, "the heads read the state: recurrence launch only");
   extern __shared__ __attribute__((aligned(16))) char smem_small_edge[];
   const int R = F + 2;                                       // rows of the folded taps: Wx | s1 | s2
   T* z = reinterpret_cast<T*>(smem_small_edge);              // [K][C][N]
@@ -58,7 +83,8 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
   T* coef = den + N;                                         // [nnzs]
   T* tvl = coef + nnzs;                                      // [nnzs]
   T* vall = tvl + nnzs;                                      // [nnz]
-  int32_t* rpl = reinterpret_cast<int32_t*>(vall + nnz);     // [N + 1]
+  T* hwl = vall + nnz;                                       // HEAD_NODE: [NC][F] node_w, then [NC] node_b (0 without one)
+  int32_t* rpl = reinterpret_cast<int32_t*>(HEAD == SE_HEAD_NODE ? hwl + NC * (F + 1) : hwl);   // [N + 1]
   int32_t* rrp = rpl + (N + 1);                              // [N + 1]
   int32_t* trp = rrp + (N + 1);                              // [N + 1]
   int32_t* coll = trp + (N + 1);                             // [nnz]
@@ -87,6 +113,10 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
     if (bias)
       for (int f2 = 0; f2 < F; ++f2) acc += attW[f * F + f2] * bias[f2];
     bf[f] = acc;
+  }
+  if (HEAD == SE_HEAD_NODE) {
+    for (int i = tid; i < NC * F; i += SE_THREADS) hwl[i] = head_w[i];
+    for (int i = tid; i < NC; i += SE_THREADS) hwl[NC * F + i] = head_b ? head_b[i] : T(0);
   }
   if (!XP)
     for (int i = tid; i < FN; i += SE_THREADS) z[i] = U[(size_t)b * FN + i];                    // z_0 = h0
@@ -133,6 +163,8 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
       }
     }
     __syncthreads();
+    // y_{t-1}: h_{t-1} is stable in z_0 from this barrier until the step's column pass writes h_t over it
+    if (HEAD == SE_HEAD_NODE && t > 0) se_node_head<T>(z, hwl, Y + ((size_t)b * Tn + (t - 1)) * NC * N, tid, N, F, NC);
     for (int k = 1; k < K; ++k) {                                                               // z_k = z_{k-1} S
       const T* zp = z + (size_t)(k - 1) * CN;
       T* zn = z + (size_t)k * CN;
@@ -195,8 +227,15 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
     // ---- column pass and the step's epilogue
     T g = T(1);
     if (gate) g = gate[(size_t)t * B + b];
-    const bool store = XP || !last_only || t == Tn - 1;
-    T* out = XP ? Ya + ((size_t)b * Tn + t) * FN : H + ((size_t)b * (last_only ? 1 : Tn) + (last_only ? 0 : t)) * FN;
+    bool store;
+    T* out;
+    if (HEAD == SE_HEAD_NONE) {
+      store = XP || !last_only || t == Tn - 1;
+      out = XP ? Ya + ((size_t)b * Tn + t) * FN : H + ((size_t)b * (last_only ? 1 : Tn) + (last_only ? 0 : t)) * FN;
+    } else {                                                                                    // last_only: GCRNN_SMALL_STATES_*
+      store = last_only == GCRNN_SMALL_STATES_ALL || (last_only == GCRNN_SMALL_STATES_LAST && t == Tn - 1);
+      out = last_only == GCRNN_SMALL_STATES_ALL ? H + ((size_t)b * Tn + t) * FN : H + (size_t)b * FN;      // (never dereferenced with _NONE)
+    }
 #pragma unroll
     for (int p = 0; p < SE_PASSES; ++p) {
       const int i = tid + p * SE_THREADS;
@@ -217,6 +256,23 @@ __global__ __launch_bounds__(1024) void small_edge_cell_kernel(
     }
     // the next step's first barrier orders the new state before the hops that read it
   }
+  if (HEAD != SE_HEAD_NONE) {
+    __syncthreads();                                                                            // h_T in z_0
+    if (HEAD == SE_HEAD_NODE) {
+      se_node_head<T>(z, hwl, Y + ((size_t)b * Tn + (Tn - 1)) * NC * N, tid, N, F, NC);
+    } else {
+      // one wave per class, lanes stride over i = f N + n; the 64 partial sums fold in a fixed xor butterfly
+      const int lane = tid & 63;
+      for (int c = tid >> 6; c < NC; c += SE_THREADS / 64) {
+        const T* wr = head_w + (size_t)c * FN;
+        T acc = T(0);
+        for (int i = lane; i < FN; i += 64) acc += wr[i] * z[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (lane == 0) Y[(size_t)b * NC + c] = acc + (head_b ? head_b[c] : T(0));
+      }
+    }
+  }
 }
 
 static size_t small_edge_lds_bytes(int dtype, int64_t N, int64_t nnz, int64_t nnzs, int64_t G, int64_t F, int64_t Kin, int64_t Kst) {
@@ -236,29 +292,98 @@ extern "C" int gcrnn_small_edge_supported(int dtype, int64_t N, int64_t nnz, int
   return small_edge_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst) <= 150 * 1024 ? 1 : 0;
 }
 
-template <typename T>
-static int small_edge_launch(const void* X, const void* h0, const void* wA, const void* wB, const void* bias, const void* att_in_w,
-                             const void* att_in_a, const void* att_f_w, const void* att_f_a, const void* gi, const void* gf,
-                             const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* s_rowptr,
-                             const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val, void* Ya,
-                             void* H, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz,
-                             int64_t nnzs, int last_only, size_t lds, hipStream_t st) {
+// the LDS values of the head: node_w | node_b of the per-node head; the read-out streams head_w from global memory
+static size_t small_edge_head_lds_bytes(int dtype, int head_kind, int64_t F, int64_t NC) {
+  return head_kind == SE_HEAD_NODE ? (dtype == GCRNN_F64 ? 8 : 4) * (size_t)(NC * (F + 1)) : 0;
+}
+
+extern "C" int gcrnn_small_edge_head_supported(int dtype, int64_t N, int64_t nnz, int64_t nnz_support, int64_t G, int64_t F,
+                                               int64_t Kin, int64_t Kst, int head_kind, int64_t NC, int backward) {
+  if (!gcrnn_small_edge_supported(dtype, N, nnz, nnz_support, G, F, Kin, Kst)) return 0;
+  if (backward && !gcrnn_small_edge_backward_supported(dtype, N, nnz, nnz_support, G, F, Kin, Kst)) return 0;
+  if (head_kind == SE_HEAD_LAST) {
+    if (NC < 1 || NC > GCRNN_SMALL_HEAD_MAX_CLASSES) return 0;
+  } else if (head_kind == SE_HEAD_NODE) {
+    if (NC < 1 || NC > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return 0;          // O N <= 8 * 128 threads: one per (o, n)
+  } else {
+    return 0;
+  }
+  return small_edge_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst) + small_edge_head_lds_bytes(dtype, head_kind, F, NC) <= 150 * 1024
+             ? 1 : 0;
+}
+
+namespace {
+struct SmallEdgeFwdArgs {
+  const void *X, *h0, *wA, *wB, *bias, *att_in_w, *att_in_a, *att_f_w, *att_f_a, *gi, *gf;
+  const int32_t *rowptr, *col;
+  const void* val;
+  const int32_t *s_rowptr, *r_edge, *t_rowptr, *t_edge;
+  const void* t_val;
+  void *Ya, *H;
+  const void *head_w, *head_b;
+  void* Y;
+  int64_t B, T, N, G, F, Kin, Kst, nnz, nnzs, NC;
+  int store;                            // HEAD_NONE: last_only; with a head: GCRNN_SMALL_STATES_*
+};
+}  // namespace
+
+template <typename T, int HEAD>
+static int small_edge_launch(const SmallEdgeFwdArgs& a, size_t lds, hipStream_t st) {
   auto kx = small_edge_cell_kernel<T, true>;
-  auto kh = small_edge_cell_kernel<T, false>;
+  auto kh = small_edge_cell_kernel<T, false, HEAD>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
-  kx<<<(unsigned)(B * Tn), SE_THREADS, lds, st>>>((const T*)X, (const T*)wA, (const T*)bias, (const T*)att_in_w, (const T*)att_in_a,
-                                                  (const T*)gi, rowptr, col, (const T*)val, s_rowptr, (const int2*)r_edge, t_rowptr,
-                                                  (const int2*)t_edge, (const T*)t_val, (T*)Ya, (T*)nullptr, (int)Tn, (int)N, (int)G,
-                                                  (int)F, (int)Kin, (int)nnz, (int)nnzs, (int)B, 0);
-  kh<<<(unsigned)B, SE_THREADS, lds, st>>>((const T*)h0, (const T*)wB, (const T*)bias, (const T*)att_f_w, (const T*)att_f_a,
-                                           (const T*)gf, rowptr, col, (const T*)val, s_rowptr, (const int2*)r_edge, t_rowptr,
-                                           (const int2*)t_edge, (const T*)t_val, (T*)Ya, (T*)H, (int)Tn, (int)N, (int)F, (int)F,
-                                           (int)Kst, (int)nnz, (int)nnzs, (int)B, last_only);
+  kx<<<(unsigned)(a.B * a.T), SE_THREADS, lds, st>>>((const T*)a.X, (const T*)a.wA, (const T*)a.bias, (const T*)a.att_in_w,
+                                                     (const T*)a.att_in_a, (const T*)a.gi, a.rowptr, a.col, (const T*)a.val, a.s_rowptr,
+                                                     (const int2*)a.r_edge, a.t_rowptr, (const int2*)a.t_edge, (const T*)a.t_val, (T*)a.Ya,
+                                                     (T*)nullptr, (const T*)nullptr, (const T*)nullptr, (T*)nullptr, (int)a.T, (int)a.N,
+                                                     (int)a.G, (int)a.F, (int)a.Kin, (int)a.nnz, (int)a.nnzs, (int)a.B, 0, 0);
+  kh<<<(unsigned)a.B, SE_THREADS, lds, st>>>((const T*)a.h0, (const T*)a.wB, (const T*)a.bias, (const T*)a.att_f_w, (const T*)a.att_f_a,
+                                             (const T*)a.gf, a.rowptr, a.col, (const T*)a.val, a.s_rowptr, (const int2*)a.r_edge,
+                                             a.t_rowptr, (const int2*)a.t_edge, (const T*)a.t_val, (T*)a.Ya, (T*)a.H, (const T*)a.head_w,
+                                             (const T*)a.head_b, (T*)a.Y, (int)a.T, (int)a.N, (int)a.F, (int)a.F, (int)a.Kst, (int)a.nnz,
+                                             (int)a.nnzs, (int)a.B, a.store, (int)a.NC);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
+}
+
+// both entry points: the validation, then the two launches. Without `head` it is gcrnn_small_edge_forward (store = last_only).
+static int small_edge_forward(int dtype, const SmallEdgeFwdArgs& a, bool head, int head_kind, void* stream) {
+  if (!a.X || !a.h0 || !a.wA || !a.wB || !a.att_in_w || !a.att_in_a || !a.att_f_w || !a.att_f_a || !a.rowptr || !a.s_rowptr ||
+      !a.t_rowptr || !a.Ya)
+    return GCRNN_ERR_NULL_POINTER;
+  if (!a.H && !(head && a.store == GCRNN_SMALL_STATES_NONE)) return GCRNN_ERR_NULL_POINTER;
+  if (head && (!a.head_w || !a.Y)) return GCRNN_ERR_NULL_POINTER;
+  if ((a.nnz > 0 && (!a.col || !a.val)) || (a.nnzs > 0 && (!a.r_edge || !a.t_edge || !a.t_val))) return GCRNN_ERR_NULL_POINTER;
+  if ((a.gi == nullptr) != (a.gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (a.B <= 0 || a.T <= 0 || a.N <= 0 || a.G <= 0 || a.F <= 0 || a.Kin <= 0 || a.Kst <= 0 || a.nnz < 0 || a.nnzs < 0)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (a.B > 2147483647LL || a.T > 2147483647LL || a.B * a.T > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
+  if (head) {
+    if (head_kind != SE_HEAD_LAST && head_kind != SE_HEAD_NODE) return GCRNN_ERR_BAD_SHAPE;
+    if (a.store != GCRNN_SMALL_STATES_ALL && a.store != GCRNN_SMALL_STATES_LAST && a.store != GCRNN_SMALL_STATES_NONE)
+      return GCRNN_ERR_BAD_SHAPE;
+    if (a.NC <= 0 || a.NC > (head_kind == SE_HEAD_NODE ? GCRNN_SMALL_NODE_HEAD_MAX_OUT : GCRNN_SMALL_HEAD_MAX_CLASSES))
+      return GCRNN_ERR_BAD_SHAPE;
+    if (!gcrnn_small_edge_head_supported(dtype, a.N, a.nnz, a.nnzs, a.G, a.F, a.Kin, a.Kst, head_kind, a.NC, 0))
+      return GCRNN_ERR_UNSUPPORTED;
+  } else if (!gcrnn_small_edge_supported(dtype, a.N, a.nnz, a.nnzs, a.G, a.F, a.Kin, a.Kst)) {
+    return GCRNN_ERR_UNSUPPORTED;
+  }
+  const size_t lds = small_edge_lds_bytes(dtype, a.N, a.nnz, a.nnzs, a.G, a.F, a.Kin, a.Kst) +
+                     small_edge_head_lds_bytes(dtype, head_kind, a.F, a.NC);
+  hipStream_t st = as_stream(stream);
+  if (dtype == GCRNN_F32) {
+    if (head_kind == SE_HEAD_LAST) return small_edge_launch<float, SE_HEAD_LAST>(a, lds, st);
+    if (head_kind == SE_HEAD_NODE) return small_edge_launch<float, SE_HEAD_NODE>(a, lds, st);
+    return small_edge_launch<float, SE_HEAD_NONE>(a, lds, st);
+  }
+  if (head_kind == SE_HEAD_LAST) return small_edge_launch<double, SE_HEAD_LAST>(a, lds, st);
+  if (head_kind == SE_HEAD_NODE) return small_edge_launch<double, SE_HEAD_NODE>(a, lds, st);
+  return small_edge_launch<double, SE_HEAD_NONE>(a, lds, st);
 }
 
 extern "C" int gcrnn_small_edge_forward(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
@@ -268,20 +393,22 @@ extern "C" int gcrnn_small_edge_forward(int dtype, const void* X, const void* h0
                                         const int32_t* t_edge, const void* t_val, void* Ya, void* H, int64_t B, int64_t T, int64_t N,
                                         int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support,
                                         int last_only, void* stream) {
-  if (!X || !h0 || !wA || !wB || !att_in_w || !att_in_a || !att_f_w || !att_f_a || !rowptr || !s_rowptr || !t_rowptr || !Ya || !H)
-    return GCRNN_ERR_NULL_POINTER;
-  if ((nnz > 0 && (!col || !val)) || (nnz_support > 0 && (!r_edge || !t_edge || !t_val))) return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
-  if (B <= 0 || T <= 0 || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0 || nnz < 0 || nnz_support < 0) return GCRNN_ERR_BAD_SHAPE;
-  if (B > 2147483647LL || T > 2147483647LL || B * T > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
-  if (!gcrnn_small_edge_supported(dtype, N, nnz, nnz_support, G, F, Kin, Kst)) return GCRNN_ERR_UNSUPPORTED;
-  const size_t lds = small_edge_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst);
-  if (dtype == GCRNN_F32)
-    return small_edge_launch<float>(X, h0, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, s_rowptr,
-                                    r_edge, t_rowptr, t_edge, t_val, Ya, H, B, T, N, G, F, Kin, Kst, nnz, nnz_support, last_only,
-                                    lds, as_stream(stream));
-  return small_edge_launch<double>(X, h0, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, s_rowptr,
-                                   r_edge, t_rowptr, t_edge, t_val, Ya, H, B, T, N, G, F, Kin, Kst, nnz, nnz_support, last_only,
-                                   lds, as_stream(stream));
+  const SmallEdgeFwdArgs a = {X, h0, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, s_rowptr, r_edge,
+                              t_rowptr, t_edge, t_val, Ya, H, nullptr, nullptr, nullptr, B, T, N, G, F, Kin, Kst, nnz, nnz_support, 0,
+                              last_only ? 1 : 0};
+  return small_edge_forward(dtype, a, false, SE_HEAD_NONE, stream);
+}
+
+extern "C" int gcrnn_small_edge_forward_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                                             const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a,
+                                             const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col, const void* val,
+                                             const int32_t* s_rowptr, const int32_t* r_edge, const int32_t* t_rowptr,
+                                             const int32_t* t_edge, const void* t_val, void* Ya, void* H, const void* head_w,
+                                             const void* head_b, void* Y, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
+                                             int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support, int64_t NC, int head_kind,
+                                             int store_states, void* stream) {
+  const SmallEdgeFwdArgs a = {X, h0, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, s_rowptr, r_edge,
+                              t_rowptr, t_edge, t_val, Ya, H, head_w, head_b, Y, B, T, N, G, F, Kin, Kst, nnz, nnz_support, NC,
+                              store_states};
+  return small_edge_forward(dtype, a, true, head_kind, stream);
 }

@@ -16,6 +16,13 @@
 // Row-ordered sums walk the support rows through `inv`, the inverse of the permutation t_pos (row position of column-ordered edge q).
 // The gradients of the FOLDED taps and bias leave in per-workgroup slots; the host side sums the slots and unfolds them.
 // No atomics, every sum in a fixed order: bit-reproducible, and a sequence's results do not depend on the rest of the batch.
+//
+// HEAD (recurrence launch only): where the step's upstream dH_t comes from.
+//   SEB_HEAD_NONE  read from dH [B][Tn][F][N]
+//   SEB_HEAD_LAST  the read-out on h_T: dH_T[i] = sum_c dlogits[b][c] head_w[c][i] (c ascending) seeds the carried dh before the time loop;
+//                  every step's own upstream is the constant 0
+//   SEB_HEAD_NODE  the per-node head on every state: dH_t[f][n] = sum_o node_w[o][f] dY[b][t][o][n] (o ascending), formed where dH is read
+// Everything behind the upstream is the same code: with an exactly representable dH the three give the same bits.
 #include "gcrnn_common.h"
 
 namespace {
@@ -28,6 +35,7 @@ constexpr int SEB_THREADS = 1024;
 constexpr int SEB_PASSES = 4;            // (F + 2) * N <= SEB_PASSES * SEB_THREADS and (F + 2) * (K * C + 1) <= SEB_PASSES * SEB_THREADS (host)
 constexpr int SEB_ROW_LANES = 8;         // lanes that share one support row / column in the list sums
 constexpr int SEB_WAVES = SEB_THREADS / 64;
+constexpr int SEB_HEAD_NONE = 0, SEB_HEAD_LAST = 1, SEB_HEAD_NODE = 2;
 
 // sum over the SEB_ROW_LANES lanes of a group, the same value in every lane, in a fixed order
 template <typename T> __device__ __forceinline__ T seb_group_sum(T v) {
@@ -38,11 +46,12 @@ template <typename T> __device__ __forceinline__ T seb_group_sum(T v) {
 
 }  // namespace
 
-template <typename T, bool XP, bool DX = false>
+template <typename T, bool XP, bool DX = false, int HEAD = SEB_HEAD_NONE>
 __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     const T* __restrict__ U,          // XP: X [B][Tn][C][N]        else: h0 [B][C][N]  (C = F)
     const T* __restrict__ Hs,         // [B][Tn][F][N] states of the forward (not XP)
-    const T* __restrict__ dH,         // [B][Tn][F][N] upstream gradient (not XP)
+    const T* __restrict__ dH,         // [B][Tn][F][N] upstream gradient (not XP); HEAD_LAST: dlogits [B][NC]; HEAD_NODE: dY [B][Tn][NC][N]
+    const T* __restrict__ head_w,     // HEAD_LAST: [NC][F N]       HEAD_NODE: [NC][F]
     const T* __restrict__ w,          // [F][K][C] filter taps
     const T* __restrict__ bias,       // [F] or null
     const T* __restrict__ attW,       // [F][F]
@@ -57,8 +66,9 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     T* __restrict__ pbf,              // [gridDim.x][R]       ... and of the folded bias
     T* __restrict__ dgate,            // [Tn][B] or null (with gate)
     T* __restrict__ dU,               // XP with DX: dX [B][Tn][C][N]   not XP: dh0 [B][F][N] or null
-    int Tn, int N, int C, int F, int K, int nnz, int nnzs, int B) {
+    int Tn, int N, int C, int F, int K, int nnz, int nnzs, int B, int NC) {
   static_assert(XP || !DX, "the gradient for X leaves the input branch");
+  static_assert(!XP || HEAD == SEB_HEAD_NONE, "the heads sit on the state: recurrence launch only");
   constexpr bool HOPS = !XP || DX;                           // the hops' adjoint runs: CSR(S) in LDS
   extern __shared__ __attribute__((aligned(16))) char smem_small_edge_bwd[];
   const int R = F + 2;
@@ -121,7 +131,16 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
       for (int f2 = 0; f2 < F; ++f2) acc += attW[f * F + f2] * bias[f2];
     bf[f] = acc;
   }
-  for (int i = tid; i < GN; i += SEB_THREADS) gbuf0[i] = T(0);                                   // dh after the last step
+  if (HEAD == SEB_HEAD_LAST) {                                                                   // dh after the last step: the read-out's dH_T (C = F: GN = FN)
+    const T* dl = dH + (size_t)b * NC;
+    for (int i = tid; i < GN; i += SEB_THREADS) {
+      T acc = T(0);
+      for (int c = 0; c < NC; ++c) acc += dl[c] * head_w[(size_t)c * FN + i];
+      gbuf0[i] = acc;
+    }
+  } else {
+    for (int i = tid; i < GN; i += SEB_THREADS) gbuf0[i] = T(0);                                 // dh after the last step
+  }
   __syncthreads();
   for (int i = tid; i < 2 * KC; i += SEB_THREADS) {
     const int h = i / KC, r = i - h * KC;
@@ -157,6 +176,17 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
     {
       const T* u0 = XP ? U + ((size_t)b * Tn + t) * CN : (t > 0 ? Hs + ((size_t)b * Tn + (t - 1)) * FN : U + (size_t)b * FN);
       for (int i = tid; i < CN; i += SEB_THREADS) z[i] = u0[i];                                 // z_0 = x_t or h_{t-1}
+    }
+    if (HEAD == SEB_HEAD_NODE) {
+      // the step's upstream dH_t[f][n] = sum_o node_w[o][f] dY[b][t][o][n], o ascending, parked in dwx (free until the column pass's adjoint):
+      // element i is written and read back by the same thread, here where few registers are live
+      const T* dyt = dH + ((size_t)b * Tn + t) * NC * N;
+      for (int i = tid; i < FN; i += SEB_THREADS) {
+        const int f = i / N, n = i - f * N;
+        T s = T(0);
+        for (int c = 0; c < NC; ++c) s += head_w[c * F + f] * dyt[c * N + n];
+        dwx[i] = s;
+      }
     }
     __syncthreads();
     // ---------------------------------------------------------------- the step's forward, as small_edge_cell_kernel
@@ -226,7 +256,11 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
       for (int p = 0; p < SEB_PASSES; ++p) {
         const int i = tid + p * SEB_THREADS;
         hv[p] = (!XP && i < FN) ? Hs[o + i] : T(0);
-        up[p] = (i < FN) ? (XP ? dPre[o + i] : dH[o + i]) : T(0);
+        if (HEAD == SEB_HEAD_NONE) {
+          up[p] = (i < FN) ? (XP ? dPre[o + i] : dH[o + i]) : T(0);
+        } else {
+          up[p] = T(0);                                       // HEAD_LAST: the constant; HEAD_NODE: formed behind the column sum below
+        }
       }
     }
 #pragma unroll
@@ -241,6 +275,7 @@ __global__ __launch_bounds__(1024) void small_edge_bptt_kernel(
         if (XP) {
           dpre = up[p];
         } else {
+          if (HEAD == SEB_HEAD_NODE) up[p] = dwx[i];          // formed on top of the step, this thread's own element
           dpre = (up[p] + cur[i]) * (T(1) - hv[p] * hv[p]);
           dPre[((size_t)b * Tn + t) * FN + i] = dpre;
         }
@@ -395,68 +430,85 @@ extern "C" int gcrnn_small_edge_backward_supported(int dtype, int64_t N, int64_t
   return small_edge_bwd_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst) <= 150 * 1024 ? 1 : 0;
 }
 
-template <typename T, bool DX>
-static int small_edge_bwd_launch(const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
-                                 const void* bias, const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a,
-                                 const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col, const void* val,
-                                 const int32_t* a_rowptr, const int32_t* a_col, const void* a_val, const int32_t* s_rowptr,
-                                 const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val,
-                                 const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf,
-                                 void* dh0, void* dX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
-                                 int64_t nnz, int64_t nnzs, size_t lds, hipStream_t st) {
+namespace {
+struct SmallEdgeBwdArgs {
+  const void *X, *h0, *H, *dH, *head_w, *wA, *wB, *bias, *att_in_w, *att_in_a, *att_f_w, *att_f_a, *gi, *gf;
+  const int32_t *rowptr, *col;
+  const void* val;
+  const int32_t *a_rowptr, *a_col;
+  const void* a_val;
+  const int32_t *s_rowptr, *r_edge, *t_rowptr, *t_edge;
+  const void* t_val;
+  const int32_t* t_pos;
+  void *dPre, *pwfA, *pbfA, *pwfB, *pbfB, *dgi, *dgf, *dh0, *dX;
+  int64_t B, T, N, G, F, Kin, Kst, nnz, nnzs, NC;
+};
+}  // namespace
+
+template <typename T, bool DX, int HEAD>
+static int small_edge_bwd_launch(const SmallEdgeBwdArgs& a, size_t lds, hipStream_t st) {
   auto kx = small_edge_bptt_kernel<T, true, DX>;
-  auto kh = small_edge_bptt_kernel<T, false>;
+  auto kh = small_edge_bptt_kernel<T, false, false, HEAD>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
-  kh<<<(unsigned)B, SEB_THREADS, lds, st>>>((const T*)h0, (const T*)H, (const T*)dH, (const T*)wB, (const T*)bias, (const T*)att_f_w,
-                                            (const T*)att_f_a, (const T*)gf, rowptr, col, (const T*)val, a_rowptr, a_col,
-                                            (const T*)a_val, s_rowptr, (const int2*)r_edge, t_rowptr, (const int2*)t_edge,
-                                            (const T*)t_val, t_pos, (T*)dPre, (T*)pwfB, (T*)pbfB, (T*)dgf, (T*)dh0, (int)Tn, (int)N,
-                                            (int)F, (int)F, (int)Kst, (int)nnz, (int)nnzs, (int)B);
+  kh<<<(unsigned)a.B, SEB_THREADS, lds, st>>>((const T*)a.h0, (const T*)a.H, (const T*)a.dH, (const T*)a.head_w, (const T*)a.wB,
+                                              (const T*)a.bias, (const T*)a.att_f_w, (const T*)a.att_f_a, (const T*)a.gf, a.rowptr, a.col,
+                                              (const T*)a.val, a.a_rowptr, a.a_col, (const T*)a.a_val, a.s_rowptr, (const int2*)a.r_edge,
+                                              a.t_rowptr, (const int2*)a.t_edge, (const T*)a.t_val, a.t_pos, (T*)a.dPre, (T*)a.pwfB,
+                                              (T*)a.pbfB, (T*)a.dgf, (T*)a.dh0, (int)a.T, (int)a.N, (int)a.F, (int)a.F, (int)a.Kst,
+                                              (int)a.nnz, (int)a.nnzs, (int)a.B, (int)a.NC);
   // the input branch reads CSR(S) only for dX
-  kx<<<(unsigned)(B * Tn), SEB_THREADS, lds, st>>>((const T*)X, (const T*)nullptr, (const T*)nullptr, (const T*)wA, (const T*)bias,
-                                                   (const T*)att_in_w, (const T*)att_in_a, (const T*)gi, rowptr, col, (const T*)val,
-                                                   DX ? a_rowptr : nullptr, DX ? a_col : nullptr, DX ? (const T*)a_val : nullptr,
-                                                   s_rowptr, (const int2*)r_edge, t_rowptr, (const int2*)t_edge, (const T*)t_val, t_pos,
-                                                   (T*)dPre, (T*)pwfA, (T*)pbfA, (T*)dgi, DX ? (T*)dX : (T*)nullptr, (int)Tn, (int)N,
-                                                   (int)G, (int)F, (int)Kin, (int)nnz, (int)nnzs, (int)B);
+  kx<<<(unsigned)(a.B * a.T), SEB_THREADS, lds, st>>>((const T*)a.X, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
+                                                      (const T*)a.wA, (const T*)a.bias, (const T*)a.att_in_w, (const T*)a.att_in_a,
+                                                      (const T*)a.gi, a.rowptr, a.col, (const T*)a.val, DX ? a.a_rowptr : nullptr,
+                                                      DX ? a.a_col : nullptr, DX ? (const T*)a.a_val : nullptr, a.s_rowptr,
+                                                      (const int2*)a.r_edge, a.t_rowptr, (const int2*)a.t_edge, (const T*)a.t_val, a.t_pos,
+                                                      (T*)a.dPre, (T*)a.pwfA, (T*)a.pbfA, (T*)a.dgi, DX ? (T*)a.dX : (T*)nullptr,
+                                                      (int)a.T, (int)a.N, (int)a.G, (int)a.F, (int)a.Kin, (int)a.nnz, (int)a.nnzs,
+                                                      (int)a.B, 0);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
 
-// both entry points: the validation, then the two launches; DX: dX is one more required pointer
-template <bool DX>
-static int small_edge_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA, const void* wB,
-                               const void* bias, const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a,
-                               const void* gi, const void* gf, const int32_t* rowptr, const int32_t* col, const void* val,
-                               const int32_t* a_rowptr, const int32_t* a_col, const void* a_val, const int32_t* s_rowptr,
-                               const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val,
-                               const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf,
-                               void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
-                               int64_t nnz, int64_t nnz_support, void* stream) {
-  if (!X || !h0 || !H || !dH || !wA || !wB || !att_in_w || !att_in_a || !att_f_w || !att_f_a || !rowptr || !a_rowptr || !s_rowptr ||
-      !t_rowptr || !dPre || !pwfA || !pbfA || !pwfB || !pbfB || (DX && !dX))
+template <typename T, bool DX>
+static int small_edge_bwd_launch_head(const SmallEdgeBwdArgs& a, int head_kind, size_t lds, hipStream_t st) {
+  if (head_kind == SEB_HEAD_LAST) return small_edge_bwd_launch<T, DX, SEB_HEAD_LAST>(a, lds, st);
+  if (head_kind == SEB_HEAD_NODE) return small_edge_bwd_launch<T, DX, SEB_HEAD_NODE>(a, lds, st);
+  return small_edge_bwd_launch<T, DX, SEB_HEAD_NONE>(a, lds, st);
+}
+
+// all entry points: the validation, then the two launches. need_dx: dX is one more required pointer (gcrnn_small_edge_backward_dx);
+// head: gcrnn_small_edge_backward_head, a.dH is the head's upstream and a.dX selects the input branch's dx variant
+static int small_edge_backward(int dtype, const SmallEdgeBwdArgs& a, bool need_dx, bool head, int head_kind, void* stream) {
+  if (!a.X || !a.h0 || !a.H || !a.dH || !a.wA || !a.wB || !a.att_in_w || !a.att_in_a || !a.att_f_w || !a.att_f_a || !a.rowptr ||
+      !a.a_rowptr || !a.s_rowptr || !a.t_rowptr || !a.dPre || !a.pwfA || !a.pbfA || !a.pwfB || !a.pbfB || (need_dx && !a.dX) ||
+      (head && !a.head_w))
     return GCRNN_ERR_NULL_POINTER;
-  if ((nnz > 0 && (!col || !val || !a_col || !a_val)) || (nnz_support > 0 && (!r_edge || !t_edge || !t_val || !t_pos)))
+  if ((a.nnz > 0 && (!a.col || !a.val || !a.a_col || !a.a_val)) || (a.nnzs > 0 && (!a.r_edge || !a.t_edge || !a.t_val || !a.t_pos)))
     return GCRNN_ERR_NULL_POINTER;
-  if ((gi == nullptr) != (gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
-  if (gi && (!dgi || !dgf)) return GCRNN_ERR_NULL_POINTER;
+  if ((a.gi == nullptr) != (a.gf == nullptr)) return GCRNN_ERR_NULL_POINTER;
+  if (a.gi && (!a.dgi || !a.dgf)) return GCRNN_ERR_NULL_POINTER;
   if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
-  if (B <= 0 || T <= 0 || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0 || nnz < 0 || nnz_support < 0) return GCRNN_ERR_BAD_SHAPE;
-  if (B > 2147483647LL || T > 2147483647LL || B * T > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
-  if (!gcrnn_small_edge_backward_supported(dtype, N, nnz, nnz_support, G, F, Kin, Kst)) return GCRNN_ERR_UNSUPPORTED;
-  const size_t lds = small_edge_bwd_lds_bytes(dtype, N, nnz, nnz_support, G, F, Kin, Kst);
+  if (a.B <= 0 || a.T <= 0 || a.N <= 0 || a.G <= 0 || a.F <= 0 || a.Kin <= 0 || a.Kst <= 0 || a.nnz < 0 || a.nnzs < 0)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (a.B > 2147483647LL || a.T > 2147483647LL || a.B * a.T > 2147483647LL) return GCRNN_ERR_BAD_SHAPE;
+  if (head) {
+    if (head_kind != SEB_HEAD_LAST && head_kind != SEB_HEAD_NODE) return GCRNN_ERR_BAD_SHAPE;
+    if (a.NC <= 0 || a.NC > (head_kind == SEB_HEAD_NODE ? GCRNN_SMALL_NODE_HEAD_MAX_OUT : GCRNN_SMALL_HEAD_MAX_CLASSES))
+      return GCRNN_ERR_BAD_SHAPE;
+    if (!gcrnn_small_edge_head_supported(dtype, a.N, a.nnz, a.nnzs, a.G, a.F, a.Kin, a.Kst, head_kind, a.NC, 1))
+      return GCRNN_ERR_UNSUPPORTED;
+  } else if (!gcrnn_small_edge_backward_supported(dtype, a.N, a.nnz, a.nnzs, a.G, a.F, a.Kin, a.Kst)) {
+    return GCRNN_ERR_UNSUPPORTED;
+  }
+  const size_t lds = small_edge_bwd_lds_bytes(dtype, a.N, a.nnz, a.nnzs, a.G, a.F, a.Kin, a.Kst);
+  hipStream_t st = as_stream(stream);
+  const bool dx = a.dX != nullptr;
   if (dtype == GCRNN_F32)
-    return small_edge_bwd_launch<float, DX>(X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
-                                            a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA,
-                                            pwfB, pbfB, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, lds,
-                                            as_stream(stream));
-  return small_edge_bwd_launch<double, DX>(X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
-                                           a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA,
-                                           pwfB, pbfB, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, lds,
-                                           as_stream(stream));
+    return dx ? small_edge_bwd_launch_head<float, true>(a, head_kind, lds, st) : small_edge_bwd_launch_head<float, false>(a, head_kind, lds, st);
+  return dx ? small_edge_bwd_launch_head<double, true>(a, head_kind, lds, st) : small_edge_bwd_launch_head<double, false>(a, head_kind, lds, st);
 }
 
 extern "C" int gcrnn_small_edge_backward(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
@@ -468,9 +520,10 @@ extern "C" int gcrnn_small_edge_backward(int dtype, const void* X, const void* h
                                          void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf, void* dh0,
                                          int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t nnz,
                                          int64_t nnz_support, void* stream) {
-  return small_edge_backward<false>(dtype, X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
-                                    a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB,
-                                    pbfB, dgi, dgf, dh0, nullptr, B, T, N, G, F, Kin, Kst, nnz, nnz_support, stream);
+  const SmallEdgeBwdArgs a = {X, h0, H, dH, nullptr, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, a_rowptr,
+                              a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB, pbfB, dgi, dgf, dh0,
+                              nullptr, B, T, N, G, F, Kin, Kst, nnz, nnz_support, 0};
+  return small_edge_backward(dtype, a, false, false, SEB_HEAD_NONE, stream);
 }
 
 extern "C" int gcrnn_small_edge_backward_dx(int dtype, const void* X, const void* h0, const void* H, const void* dH, const void* wA,
@@ -482,7 +535,24 @@ extern "C" int gcrnn_small_edge_backward_dx(int dtype, const void* X, const void
                                             void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi, void* dgf, void* dh0,
                                             void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
                                             int64_t nnz, int64_t nnz_support, void* stream) {
-  return small_edge_backward<true>(dtype, X, h0, H, dH, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val,
-                                   a_rowptr, a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB,
-                                   pbfB, dgi, dgf, dh0, dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, stream);
+  const SmallEdgeBwdArgs a = {X, h0, H, dH, nullptr, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, a_rowptr,
+                              a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB, pbfB, dgi, dgf, dh0,
+                              dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, 0};
+  return small_edge_backward(dtype, a, true, false, SEB_HEAD_NONE, stream);
+}
+
+extern "C" int gcrnn_small_edge_backward_head(int dtype, const void* X, const void* h0, const void* H, const void* up, const void* head_w,
+                                              const void* wA, const void* wB, const void* bias, const void* att_in_w,
+                                              const void* att_in_a, const void* att_f_w, const void* att_f_a, const void* gi,
+                                              const void* gf, const int32_t* rowptr, const int32_t* col, const void* val,
+                                              const int32_t* a_rowptr, const int32_t* a_col, const void* a_val, const int32_t* s_rowptr,
+                                              const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val,
+                                              const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB, void* dgi,
+                                              void* dgf, void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
+                                              int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support, int64_t NC, int head_kind,
+                                              void* stream) {
+  const SmallEdgeBwdArgs a = {X, h0, H, up, head_w, wA, wB, bias, att_in_w, att_in_a, att_f_w, att_f_a, gi, gf, rowptr, col, val, a_rowptr,
+                              a_col, a_val, s_rowptr, r_edge, t_rowptr, t_edge, t_val, t_pos, dPre, pwfA, pbfA, pwfB, pbfB, dgi, dgf, dh0,
+                              dX, B, T, N, G, F, Kin, Kst, nnz, nnz_support, NC};
+  return small_edge_backward(dtype, a, false, true, head_kind, stream);
 }

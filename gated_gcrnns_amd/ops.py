@@ -3513,6 +3513,191 @@ def small_edge_cell_train(X, h0, wA, wB, bias, graph, att_in, att_f, gi=None, gf
     return _SmallEdgeCell.apply(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, graph)
 
 
+# ---- the edge-gated models on small graphs: the read-out on the last state / the per-node head inside the recurrence launches
+SMALL_EDGE_HEAD_LAST, SMALL_EDGE_HEAD_NODE = 1, 2                     # gcrnn.h: GCRNN_SMALL_EDGE_HEAD_*
+
+
+def small_edge_head_supported(N, nnz, nnz_support, G, F, Kin, Kst, head_kind, NC, dtype, backward, E=1):
+    """The one-launch edge-gated kernels take this cell with a head inside the recurrence launches (gcrnn_small_edge_head_supported):
+    head_kind SMALL_EDGE_HEAD_LAST, NC classes read out of the last state, or SMALL_EDGE_HEAD_NODE, NC <= 8 outputs per node on every
+    state. backward: the training step (never more than small_edge_training_supported admits)."""
+    if E != 1 or dtype not in (torch.float32, torch.float64):
+        return False
+    return bool(lib.gcrnn_small_edge_head_supported(dtype_code(dtype), int(N), int(nnz), int(nnz_support), int(G), int(F), int(Kin),
+                                                    int(Kst), int(head_kind), int(NC), int(bool(backward))))
+
+
+def _small_edge_forward_head(X, h0, wA, wB, bias, graph, att_in, att_f, gi, gf, head_kind, head_w, head_b, store):
+    """The two launches of gcrnn_small_edge_forward_head: (H or None, logits [B][NC] / Y [B][T][NC][N]). Every operand is a named local up
+    to the launch (_small_dense_bptt)."""
+    require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], head_w, head_b)
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    dt, dev = X.dtype, X.device
+    csr = graph.fwd[0]
+    plan = graph.edge_plan()
+    nnzs = plan['nnz']
+    NC = head_w.shape[0]
+    for mixer, weight in (att_in, att_f):
+        assert tuple(mixer.shape) == (1, 1, 2 * F) and tuple(weight.shape) == (1, 1, F, F), 'one head, one edge feature, F -> F'
+    assert tuple(head_w.shape) == ((NC, F * N) if head_kind == SMALL_EDGE_HEAD_LAST else (NC, F)) and head_w.dtype == dt
+    assert head_b is None or (head_b.dtype == dt and head_b.numel() == NC)
+    if not small_edge_head_supported(N, csr.nnz, nnzs, G, F, Kin, Kst, head_kind, NC, dt, False, graph.E):
+        raise GcrnnError('small_edge head: shape outside the one-launch edge-gated kernel with a head (small_edge_head_supported)')
+    H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
+    Ya = torch.empty((B, T, F, N), dtype=dt, device=dev)              # the first launch's output, the second one's input; not kept
+    out = torch.empty((B, NC) if head_kind == SMALL_EDGE_HEAD_LAST else (B, T, NC, N), dtype=dt, device=dev)
+    bvec = bias.detach().contiguous().view(-1) if bias is not None else None
+    if gi is not None:
+        assert tuple(gi.shape) == (T, B) and tuple(gf.shape) == (T, B)
+        gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
+    Xc, h0c, wAc, wBc = X.detach().contiguous(), h0.detach().contiguous(), wA.detach().contiguous(), wB.detach().contiguous()
+    wi, ai, wfo, afo = [t.detach().contiguous() for t in (att_in[1], att_in[0], att_f[1], att_f[0])]
+    hw = head_w.detach().contiguous()
+    hb = head_b.detach().contiguous() if head_b is not None else None
+    assert all(t.dtype == dt for t in (Xc, h0c, wAc, wBc, wi, ai, wfo, afo)) and (bvec is None or bvec.dtype == dt)
+    vals, tvals = csr.val(dt), _edge_support_values(graph, dt)
+    check(lib.gcrnn_small_edge_forward_head(dtype_code(dt), _p(Xc), _p(h0c), _p(wAc), _p(wBc), _p(bvec), _p(wi), _p(ai), _p(wfo), _p(afo),
+                                            _p(gi), _p(gf), _p(csr.rowptr), _p(csr.col), _p(vals), _p(plan['rowptr']), _p(plan['r_edge']),
+                                            _p(plan['t_rowptr']), _p(plan['t_edge']), _p(tvals), _p(Ya), _p(H), _p(hw), _p(hb), _p(out),
+                                            B, T, N, G, F, Kin, Kst, csr.nnz, nnzs, NC, head_kind, store, _stream()),
+          'small_edge_forward_head')
+    return H, out
+
+
+def _small_edge_bptt_head(ctx, head_kind, up, head_w):
+    """The two BPTT launches of gcrnn_small_edge_backward_head from what the forward saved, and the unfolding of the folded taps'
+    gradients: the gradients of _SmallEdgeCell.backward (dX .. dgf). up: dlogits [B][NC] or dY [B][T][NC][N], contiguous."""
+    X, h0, H, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf = ctx.saved_tensors[:12]
+    B, T, G, N = X.shape
+    F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+    dt, dev = X.dtype, X.device
+    graph = ctx.graph
+    fwd, adj, plan = graph.fwd[0], graph.adj[0], graph.edge_plan()
+    nnzs = plan['nnz']
+    NC = head_w.shape[0]
+    if not small_edge_head_supported(N, fwd.nnz, nnzs, G, F, Kin, Kst, head_kind, NC, dt, True, graph.E):
+        raise GcrnnError('small_edge head: shape outside the edge-gated BPTT kernel with a head (small_edge_head_supported, backward)')
+    R = F + 2
+    dPre = torch.empty((B, T, F, N), dtype=dt, device=dev)
+    pwfA = torch.empty((B * T, R, Kin, G), dtype=dt, device=dev)
+    pbfA = torch.empty((B * T, R), dtype=dt, device=dev)
+    pwfB = torch.empty((B, R, Kst, F), dtype=dt, device=dev)
+    pbfB = torch.empty((B, R), dtype=dt, device=dev)
+    dgi = dgf = None
+    if gi is not None:
+        gi, gf = gi.to(dt).contiguous(), gf.to(dt).contiguous()
+        dgi = torch.empty((T, B), dtype=dt, device=dev)
+        dgf = torch.empty((T, B), dtype=dt, device=dev)
+    dh0 = torch.empty_like(h0) if ctx.needs_input_grad[1] else None
+    dX = torch.empty_like(X) if ctx.needs_input_grad[0] else None
+    bvec = bias.contiguous().view(-1) if bias is not None else None
+    assert up.is_contiguous() and head_w.is_contiguous()
+    wAc, wBc = wA.contiguous(), wB.contiguous()
+    wi, ai, wfo, afo = w_in.contiguous(), m_in.contiguous(), w_f.contiguous(), m_f.contiguous()
+    fval, aval, tvals = fwd.val(dt), adj.val(dt), _edge_support_values(graph, dt)
+    check(lib.gcrnn_small_edge_backward_head(dtype_code(dt), _p(X), _p(h0), _p(H), _p(up), _p(head_w), _p(wAc), _p(wBc), _p(bvec), _p(wi),
+                                             _p(ai), _p(wfo), _p(afo), _p(gi), _p(gf), _p(fwd.rowptr), _p(fwd.col), _p(fval),
+                                             _p(adj.rowptr), _p(adj.col), _p(aval), _p(plan['rowptr']), _p(plan['r_edge']),
+                                             _p(plan['t_rowptr']), _p(plan['t_edge']), _p(tvals), _p(plan['t_pos']), _p(dPre), _p(pwfA),
+                                             _p(pbfA), _p(pwfB), _p(pbfB), _p(dgi), _p(dgf), _p(dh0), _p(dX), B, T, N, G, F, Kin, Kst,
+                                             fwd.nnz, nnzs, NC, head_kind, _stream()), 'small_edge_backward_head')
+    dwA, dbA, dm_in, dw_in = _edge_unfold(pwfA, pbfA, wAc, bias, ai, wi)
+    dwB, dbB, dm_f, dw_f = _edge_unfold(pwfB, pbfB, wBc, bias, afo, wfo)
+    db = dbA + dbB if bias is not None else None                  # one bias, both branches
+    return dX, dh0, dwA, dwB, db, dm_in, dw_in, dm_f, dw_f, dgi, dgf
+
+
+class _SmallEdgeCellHead(torch.autograd.Function):
+    """Edge-gated small-graph cell + Linear(F N -> C) on its last state as ONE autograd node. Forward: the two launches, every state kept
+    (BPTT reads them), the logits from the recurrence launch. Backward: the two BPTT launches, the recurrence seeded from dlogits inside
+    the kernel (gcrnn_small_edge_backward_head: no dH [B][T][F][N] is allocated, zero-filled or read), plus the library product for the
+    head's own parameters."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf, head_w, head_b, graph):
+        X, h0 = X.contiguous(), h0.contiguous()
+        H, logits = _small_edge_forward_head(X, h0, wA, wB, bias, graph, (m_in, w_in), (m_f, w_f), gi, gf, SMALL_EDGE_HEAD_LAST, head_w,
+                                             head_b, SMALL_STATES_ALL)
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf, head_w)
+        ctx.graph, ctx.has_hb = graph, head_b is not None
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        X, H, head_w = ctx.saved_tensors[0], ctx.saved_tensors[2], ctx.saved_tensors[12]
+        B, F, N = X.shape[0], H.shape[2], H.shape[3]
+        dlc, hw = dlogits.contiguous(), head_w.detach().contiguous()
+        grads = _small_edge_bptt_head(ctx, SMALL_EDGE_HEAD_LAST, dlc, hw)
+        dhw = dlc.t().mm(H[:, -1].reshape(B, F * N)) if ctx.needs_input_grad[11] else None
+        dhb = dlc.sum(dim=0) if ctx.has_hb and ctx.needs_input_grad[12] else None
+        return grads + (dhw, dhb, None)
+
+
+class _SmallEdgeCellNodeHead(torch.autograd.Function):
+    """Edge-gated small-graph cell + Linear(F -> O) shared by all nodes on every state as ONE autograd node. Forward: the two launches,
+    every state kept, Y from the recurrence launch. Backward: the two BPTT launches, the recurrence forming dH_t = node_w^T dY_t inside the
+    kernel (gcrnn_small_edge_backward_head: no dH [B][T][F][N] is allocated, written or read), plus the head's own gradients as
+    _SmallCellNodeHead makes them."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf, node_w, node_b, graph):
+        X, h0 = X.contiguous(), h0.contiguous()
+        H, Y = _small_edge_forward_head(X, h0, wA, wB, bias, graph, (m_in, w_in), (m_f, w_f), gi, gf, SMALL_EDGE_HEAD_NODE, node_w, node_b,
+                                        SMALL_STATES_ALL)
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, m_in, w_in, m_f, w_f, gi, gf, node_w)
+        ctx.graph, ctx.has_nb = graph, node_b is not None
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, H, node_w = ctx.saved_tensors[0], ctx.saved_tensors[2], ctx.saved_tensors[12]
+        B, T, F, N = H.shape
+        O = node_w.shape[0]
+        dt, dev = X.dtype, X.device
+        dYc, nw = dY.contiguous(), node_w.detach().contiguous()
+        grads = _small_edge_bptt_head(ctx, SMALL_EDGE_HEAD_NODE, dYc, nw)
+        dnw = dnb = None
+        want_nb = ctx.has_nb and ctx.needs_input_grad[12]
+        if ctx.needs_input_grad[11] and node_linear_supported(F, O, dt):
+            # node_linear's own backward kernel with dh = NULL: one pass over H and dY into per-block slots (_SmallCellNodeHead)
+            nblk = int(lib.gcrnn_node_linear_blocks(B * T, N))
+            pw = torch.empty((nblk, O, F), dtype=dt, device=dev)
+            pnb = torch.empty((nblk, O), dtype=dt, device=dev)
+            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(H), _p(nw), _p(dYc), None, _p(pw), _p(pnb), B * T, N, F, O, _stream()),
+                  'node_linear_backward')
+            dnw = pw.sum(dim=0)
+            dnb = pnb.sum(dim=0) if want_nb else None
+        else:
+            if ctx.needs_input_grad[11]:                  # F beyond node_linear's kernel: a batched product on views
+                dnw = torch.bmm(dYc.view(B * T, O, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
+            dnb = dYc.sum(dim=(0, 1, 3)) if want_nb else None
+        return grads + (dnw, dnb, None)
+
+
+def _small_edge_cell_head(fn, head_kind, X, h0, wA, wB, bias, graph, att_in, att_f, head_w, head_b, gi, gf):
+    require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], head_w)
+    operands = (X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, head_w, head_b)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
+        return _small_edge_forward_head(X, h0, wA, wB, bias, graph, att_in, att_f, gi, gf, head_kind, head_w, head_b, SMALL_STATES_NONE)[1]
+    return fn.apply(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, head_w, head_b, graph)
+
+
+def small_edge_cell_classify(X, h0, wA, wB, bias, graph, att_in, att_f, head_w, head_b, gi=None, gf=None):
+    """The edge-gated small-graph cell followed by Linear(F N -> C) on its last state (head_w [C][F*N], head_b [C] or None, the states'
+    dtype): logits [B][C]. att_in / att_f: (mixer, weight) of the input / forget attention; gi / gf: time gates [T][B] or None. Where
+    nothing wants a gradient it is one forward call that stores no state; otherwise one autograd node (_SmallEdgeCellHead) with gradients
+    for everything that wants one, X included. Shapes: small_edge_head_supported."""
+    return _small_edge_cell_head(_SmallEdgeCellHead, SMALL_EDGE_HEAD_LAST, X, h0, wA, wB, bias, graph, att_in, att_f, head_w, head_b, gi, gf)
+
+
+def small_edge_cell_regress(X, h0, wA, wB, bias, graph, att_in, att_f, node_w, node_b, gi=None, gf=None):
+    """The edge-gated small-graph cell followed by Linear(F -> O) shared by all nodes on every state (node_w [O][F], node_b [O] or None,
+    the states' dtype): Y [B][T][O][N]. Otherwise as small_edge_cell_classify (_SmallEdgeCellNodeHead). Shapes: small_edge_head_supported."""
+    return _small_edge_cell_head(_SmallEdgeCellNodeHead, SMALL_EDGE_HEAD_NODE, X, h0, wA, wB, bias, graph, att_in, att_f, node_w, node_b,
+                                 gi, gf)
+
+
 # ------------------------------------------------------------------------------------------ per-node head
 def node_linear_supported(F, O, dtype, N=None, wdtype=None):
     if dtype == torch.bfloat16:            # bf16 activations (the fused cell's output), fp32 master or bf16 parameters

@@ -910,6 +910,47 @@ int gcrnn_small_edge_backward_dx(int dtype, const void* X, const void* h0, const
                                  void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
                                  int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support, void* stream);
 
+/* The edge-gated small-graph cell with the model's output head inside its recurrence launches, so that the two-module path's
+ * B T F N buffers (the stored states in inference, dH in training) never exist. The input-branch launches are those of the entries above.
+ *   head_kind GCRNN_SMALL_EDGE_HEAD_LAST: the classification read-out Linear(F N -> NC) on h_T (replaces reference
+ *     architectures.py:1844-1856): head_w [NC][F*N], head_b [NC] or NULL, Y = logits [B][NC], up = dlogits [B][NC].
+ *     logits[b][c] = sum_i head_w[c][i] h_T[b][i] + head_b[c], one wave per class, lanes stride over i, fixed xor butterfly.
+ *     Backward: dH_T[i] = sum_c dlogits[b][c] head_w[c][i] (c ascending) seeds the carried adjoint before the time loop.
+ *   head_kind GCRNN_SMALL_EDGE_HEAD_NODE: the regression model's `multipMlp` head, one Linear(F -> NC) shared by all nodes on every
+ *     state (replaces reference architectures.py:1616-1627): head_w [NC][F], head_b [NC] or NULL, Y [B][T][NC][N], up = dY [B][T][NC][N].
+ *     Y[b][t][o][n] = head_b[o] + sum_f head_w[o][f] h_t[b][f][n] (from the bias, f ascending: gcrnn_node_linear_forward's order), one
+ *     thread per (o, n) on the state in LDS; the NC (F + 1) head values live in LDS.
+ *     Backward: dH_t[f][n] = sum_o head_w[o][f] dY[b][t][o][n] (o ascending), formed where gcrnn_small_edge_backward reads dH.
+ * gcrnn_small_edge_forward_head: the arguments of gcrnn_small_edge_forward with store_states (GCRNN_SMALL_STATES_ALL: H [B][T][F][N],
+ *   _LAST: H [B][1][F][N], _NONE: H unused and may be NULL) in place of last_only; every stored state has the bits of
+ *   gcrnn_small_edge_forward. No atomics: two runs give the same bits.
+ * gcrnn_small_edge_backward_head: the arguments of gcrnn_small_edge_backward_dx with `up`, head_w in place of dH and a nullable dX (NULL
+ *   launches the plain input branch); the results are those of gcrnn_small_edge_backward(_dx) fed the dH the head implies. The gradients
+ *   of head_w / head_b are the caller's.
+ * gcrnn_small_edge_head_supported: head_kind LAST with 1 <= NC <= GCRNN_SMALL_HEAD_MAX_CLASSES or NODE with 1 <= NC <=
+ *   GCRNN_SMALL_NODE_HEAD_MAX_OUT, gcrnn_small_edge_supported, with `backward` gcrnn_small_edge_backward_supported too, and the forward's
+ *   LDS image plus the head's values within 150 KiB. Answers without a device.
+ * Checked before any launch, in this order: GCRNN_ERR_NULL_POINTER, GCRNN_ERR_BAD_DTYPE, GCRNN_ERR_BAD_SHAPE (also an unknown head_kind
+ * or store_states, NC <= 0 or above the maximum), GCRNN_ERR_UNSUPPORTED where the query says no. */
+enum { GCRNN_SMALL_EDGE_HEAD_LAST = 1, GCRNN_SMALL_EDGE_HEAD_NODE = 2 };
+int gcrnn_small_edge_head_supported(int dtype, int64_t N, int64_t nnz, int64_t nnz_support, int64_t G, int64_t F, int64_t Kin,
+                                    int64_t Kst, int head_kind, int64_t NC, int backward);
+int gcrnn_small_edge_forward_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                                  const void* att_in_w, const void* att_in_a, const void* att_f_w, const void* att_f_a, const void* gi,
+                                  const void* gf, const int32_t* rowptr, const int32_t* col, const void* val, const int32_t* s_rowptr,
+                                  const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge, const void* t_val, void* Ya,
+                                  void* H, const void* head_w, const void* head_b, void* Y, int64_t B, int64_t T, int64_t N, int64_t G,
+                                  int64_t F, int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support, int64_t NC, int head_kind,
+                                  int store_states, void* stream);
+int gcrnn_small_edge_backward_head(int dtype, const void* X, const void* h0, const void* H, const void* up, const void* head_w,
+                                   const void* wA, const void* wB, const void* bias, const void* att_in_w, const void* att_in_a,
+                                   const void* att_f_w, const void* att_f_a, const void* gi, const void* gf, const int32_t* rowptr,
+                                   const int32_t* col, const void* val, const int32_t* a_rowptr, const int32_t* a_col, const void* a_val,
+                                   const int32_t* s_rowptr, const int32_t* r_edge, const int32_t* t_rowptr, const int32_t* t_edge,
+                                   const void* t_val, const int32_t* t_pos, void* dPre, void* pwfA, void* pbfA, void* pwfB, void* pbfB,
+                                   void* dgi, void* dgf, void* dh0, void* dX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
+                                   int64_t Kin, int64_t Kst, int64_t nnz, int64_t nnz_support, int64_t NC, int head_kind, void* stream);
+
 /* ==== per-node output head=========================================================================================
  * mlpType = 'multipMlp' of GatedGCRNNforRegression (architectures.py:1616-1627: one Linear(F -> O) applied to every node's
  * state in a Python loop over nodes), on the user layout: h [R][F][N] -> y [R][O][N], R = B * T, F <= 64, O <= 8, F32 / F64.
