@@ -184,6 +184,20 @@ class GatedGCRNNforRegression(_GatedGCRNNBase):
     def forward(self, x, h0):
         batchSize, seqLength = x.shape[0], x.shape[1]
         if self.gnn_head:
+            sel = self.outputNN[0]
+            if sel.L == 1 and list(sel.F) == [self.F_h, 1] and len(sel.dimLayersMLP) == 0 and sel.GFL[0].weight.dtype == x.dtype:
+                # a head of ONE graph-filter layer with one output feature on a small graph: y_t from the hop levels of the state still
+                # in the forward launch's LDS, dH_t formed inside the BPTT launch from the head's adjoint -- neither the T states
+                # (inference) nor dH (training) are materialised; None: not that path
+                gfl, sigma = sel.GFL[0], sel.GFL[1]
+                act = _FUSED_ACTIVATIONS.get(type(sigma))
+                y = self.stateGCRNN.regress_gnn(x, h0, gfl.weight, gfl.bias, act)      # B x T x 1 x N
+                if y is not None:
+                    if act is None:
+                        y = sigma(y)
+                    for layer in self.outputNN[1:]:                  # finalNonlinearity, where there is one
+                        y = layer(y)
+                    return y
             # the Selection-GNN head on all B*T states (reference :1630-1632): H [B][T][F_h][N] is already its [items][F][N] input
             H = self.stateGCRNN(x, h0)
             flatY = self.outputNN(H.reshape(-1, self.F_h, self.N))

@@ -856,6 +856,48 @@ class GGCRNNCell(nn.Module):
                                          ops.SMALL_EDGE_HEAD_NODE, ops.small_edge_cell_regress)
         return ops.small_cell_regress(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
 
+    @staticmethod
+    def _small_gnn_head_pays(X, backward):
+        """Where the graph-filter head inside the matrix-core forward is no slower than the two-module path (the acceptance rule of
+        DESIGN 4.10 - 4.12 on tools/small_gnn_head_bench.py's rows). backward: the training step (forward launch, adjoint
+        kernel, BPTT launch) against the cell's two launches + graph_filter_layer's two; else inference with no state stored against
+        the all-states launch + graph_filter_layer. Measured at the k-step driver's shape (N = 80, F = 20, K = K_o = 5, B = 100), this path /
+        the switched-off path in one process, median ms. Inference passes in all twelve rows at T >= 20, by 2.8 .. 10.6 % (fp32 un-gated
+        T = 200 1.980 / 2.190, fp64 2.889 / 3.163), and stays on at every T. The training step passes in all six rows at T = 200, by
+        0.4 .. 2.9 % (fp32 un-gated 6.415 / 6.604, fp64 9.416 / 9.470), and fails in five of six at T = 20, un-gated / time / node:
+        fp32 0.769 / 0.758, 1.349 / 1.343, 2.150 / 2.138, fp64 1.060 / 1.031, 1.860 / 1.840 (3.011 / 3.002 passes inside the off spread):
+        the adjoint kernel and node_linear's slot kernel are two launches where graph_filter_layer's backward is one, and the dH they
+        save is small there. So training is dispatched from T = 200 up, the length it was measured to pay at; shorter sequences keep
+        the two-module path (T = 5 is host time and bimodal: nothing is claimed). GCRNN_SMALL_GNN_HEAD=all takes them all the same
+        (the training step's peak memory falls by a third: 354.6 against 540.1 MB in fp64 at T = 200)."""
+        return not backward or X.shape[1] >= 200
+
+    def regress_gnn(self, X, h0, weight, bias, act):
+        """Cell + one graph-filter layer GraphFilter(F -> 1, K_o) + activation on EVERY state (the regression model's Selection-GNN head
+        with dimNodeSignals = [F, 1], nFilterTaps = [K_o], NoPool, no MLP; reference architectures.py:1588-1604, 1630-1632) inside the
+        small-graph matrix-core launches (ops.small_cell_regress_gnn): un-gated, time-gated, node-gated and time+node-gated cells,
+        fp32 / fp64, E = 1. weight: the GraphFilter's F_out x E x K_o x F parameter with F_out = E = 1, bias 1 x 1 or None, act a key of
+        ops._GFL_ACTS. Inference: one launch for recurrence and y, no state is stored. Training: the forward launch stores the states
+        BPTT reads and makes y; the head's adjoint kernel makes dU [B][T][K_o][N] and the BPTT launch forms dH_t from it, so the
+        dH [B][T][F][N] of the two-module path never exists. Returns y B x T x 1 x N, or None when this cell / input / head does not run
+        on that path (the model then continues on forward() + SelectionGNN). GCRNN_NO_SMALL_GNN_HEAD=1 (read at every call) switches it
+        off: A/B against the two-module path. GCRNN_SMALL_GNN_HEAD=all takes every supported row, also those _small_gnn_head_pays
+        leaves to the two-module path (the measurement's own switch)."""
+        every = os.environ.get('GCRNN_SMALL_GNN_HEAD') == 'all'
+        if weight.dim() != 4 or weight.shape[0] != 1 or weight.shape[1] != 1 or self.E != 1 or act not in ops._GFL_ACTS:
+            return None
+        if bias is not None and bias.numel() != 1:
+            return None
+        # (a view, not weight[0, 0]: the backward of an index is a zero-fill and a copy per level, four launches a step)
+        taps = weight.reshape(weight.shape[2], weight.shape[3])
+        route = self._small_head_route(X, h0, taps, bias.view(1) if bias is not None else None, 'GCRNN_NO_SMALL_GNN_HEAD',
+                                       lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
+                                       lambda x: every or self._small_gnn_head_pays(x, False), ops.small_gnn_head_supported)
+        if route is None or (route[0] and not every and not self._small_gnn_head_pays(X, True)):
+            return None
+        return ops.small_cell_regress_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps,
+                                          bias.view(1) if bias is not None else None, act, route[1], route[2])
+
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----
     def _use_fused(self, X, h0):
         if self._wants_grad(X, h0):

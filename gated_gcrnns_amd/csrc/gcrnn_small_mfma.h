@@ -37,6 +37,10 @@ __host__ __device__ inline int lds_stride(int n) {
   return s;
 }
 
+// LDS image of gcrnn_small_gnn_head_adjoint (gcrnn_small_gnn_head.hip): S^T [N][N] and two rows [N] for each of its four waves
+template <typename T>
+inline size_t gnn_adjoint_lds(int64_t N) { return sizeof(T) * ((size_t)N * (size_t)N + 8 * (size_t)N); }
+
 // acc += sum over `ksteps` k-steps of A(i, k) B(k, j): ap / bp point at this lane's element of k-step 0 and advance by
 // astep / bstep elements per k-step. Branch-free (masked lanes point at a row of zeros) and batched by four so that
 // eight LDS reads are in flight before the dependent MFMA chain consumes them.

@@ -28,8 +28,19 @@ namespace {
 // MODE = FWD_LAST adds the choice of stored states and the read-out on the last state; MODE = FWD_NODE has the choice of stored states and
 // the per-node head on EVERY state: Y[b][t][o][n] = sum_f node_w[o][f] h_t[f][n] + node_b[o] (f ascending), with node_w / node_b / Y / O in
 // the places of head_w / head_b / logits / NC. The per-step arithmetic is the same code; the mode is a template parameter because a runtime
-// head branch costs the MAXT = 4 instantiations scratch.
-enum { FWD_PLAIN = 0, FWD_LAST = 1, FWD_NODE = 2 };
+// head branch costs the MAXT = 4 instantiations scratch. MODE = FWD_GNN has the choice of stored states and a one-layer graph-filter head
+// on EVERY state: Y[b][t][0][n] = act(head_b + sum_{k < NC} sum_f head_w[k][f] (h_t S^k)[f][n]) (k ascending, f ascending), NC = K_o its
+// number of taps. (h_t S^k) are the state rows of hop level k of step t + 1, so the head shifts nothing of its own while K_o <= K; the
+// levels K .. K_o - 1 are shifted for the state rows alone into ZX, outside the rows the tap MFMAs read.
+enum { FWD_PLAIN = 0, FWD_LAST = 1, FWD_NODE = 2, FWD_GNN = 3 };
+
+// the graph-filter layer's activations in its codes (ops._GFL_ACTS): 0 identity, 1 ReLU, 2 tanh, 3 sigmoid
+template <typename T> __device__ __forceinline__ T dense_gnn_act(T v, int act) {
+  if (act == 1) return v <= T(0) ? T(0) : v;      // (as torch.relu: a NaN stays a NaN)
+  if (act == 2) return tanh(v);
+  if (act == 3) return T(1) / (T(1) + exp(-v));
+  return v;
+}
 
 template <typename T, int MAXT, int MODE>
 __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
@@ -43,10 +54,11 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     T* __restrict__ H,             // [B][Tn][F][N] (store == 0), [B][1][F][N] (store == 1) or unused (store == 2)
     int Tn, int N, int G, int F, int Kin, int Kst, int B,
     int64_t gsb, int64_t gst, int64_t gsn,       // gate element (b, t, n) sits at b gsb + t gst + n gsn
-    const T* __restrict__ head_w,  // [NC][F N] read-out on the last state (nn.Linear weight, row-major over (f, n)) or null | FWD_NODE: [NC][F]
-    const T* __restrict__ head_b,  // [NC] or null
-    T* __restrict__ logits,        // [B][NC] (with head_w) | FWD_NODE: Y [B][Tn][NC][N]
-    int NC, int store) {           // store: GCRNN_SMALL_STATES_ALL / _LAST / _NONE
+    const T* __restrict__ head_w,  // [NC][F N] read-out on the last state (nn.Linear weight, row-major over (f, n)) or null | FWD_NODE, FWD_GNN: [NC][F]
+    const T* __restrict__ head_b,  // [NC] or null | FWD_GNN: [1] or null
+    T* __restrict__ logits,        // [B][NC] (with head_w) | FWD_NODE: Y [B][Tn][NC][N] | FWD_GNN: Y [B][Tn][1][N]
+    int NC, int store,             // store: GCRNN_SMALL_STATES_ALL / _LAST / _NONE
+    int act) {                     // FWD_GNN: the head's activation (dense_gnn_act)
   constexpr bool EXT = MODE != FWD_PLAIN;
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
@@ -61,6 +73,9 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
   T* zrow = W + (size_t)F16 * KCs;                 // [Ns] zeros: what masked lanes read
   T* gvec = zrow + Ns;                             // [2][Ns] gates of this step: input-filter | state-filter, per node
   T* hw = gvec + 2 * Ns;                           // FWD_NODE: [NC][F + 1] the head's weights, its bias in column F (dense_node_head_lds)
+                                                   // FWD_GNN: [NC][F] the head's taps, then its bias (dense_gnn_head_lds)
+  const int F4 = (F + 3) & ~3;
+  T* ZX = hw + ((NC * F + 1 + 3) & ~3);            // FWD_GNN: [NC - K][F4][Ns] state rows of the hop levels K .. NC - 1
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int b = blockIdx.x;
@@ -88,12 +103,61 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     }
   };
 
+  // FWD_GNN: the state rows of hop level k (rows k C + G .. of Z, or ZX beyond the cell's own levels), and the hop of those rows alone
+  // into level k: the tiles of the state write-back, A = level k - 1 (rows >= F read zeros), B = S.
+  auto gnn_level = [&](int k) -> T* { return k < K ? Z + (size_t)(k * C + G) * Ns : ZX + (size_t)(k - K) * F4 * Ns; };
+  auto gnn_state_hop = [&](int k) {
+    const T* zp = gnn_level(k - 1);
+    T* zn = gnn_level(k);
+    for (int tile = wave; tile < (F16 >> 4) * ((N + 15) >> 4); tile += 16) {
+      const int tn = (N + 15) >> 4;
+      const int i0 = (tile / tn) << 4, j0 = (tile % tn) << 4;
+      acc_t acc = {0, 0, 0, 0};
+      const T* ap = (i0 + li < F) ? zp + (i0 + li) * Ns + lk : zrow + lk;
+      acc = tile_mac<T>(acc, ap, 4, S + lk * Ns + j0 + li, 4 * Ns, N4 >> 2);
+      const int n = j0 + li;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int f = i0 + Mf<T>::row(lane, r);
+        if (f < F && n < N) zn[f * Ns + n] = acc[r];
+      }
+    }
+  };
+  // FWD_GNN: y_t from the state rows of all NC levels, one thread per node taken from the END of the block as node_head's are. It reads
+  // the state rows only -- never the x rows of the same levels, which hold x_{t+1} by then -- and runs after the last hop barrier of step
+  // t + 1 and before the barrier behind that step's taps, where nothing writes those rows. From the bias, k ascending, f ascending.
+  auto gnn_head = [&](int t) {
+    T* yt = logits + ((size_t)b * Tn + t) * N;
+    for (int n = 1023 - tid; n < N; n += 1024) {
+      T s = hw[NC * F];
+      for (int k = 0; k < NC; ++k) {
+        const T* wr = hw + k * F;
+        const T* zr = gnn_level(k) + n;
+        int f = 0;
+        for (; f + 4 <= F; f += 4) {
+          const T w0 = wr[f], w1 = wr[f + 1], w2 = wr[f + 2], w3 = wr[f + 3];
+          const T z0 = zr[f * Ns], z1 = zr[(f + 1) * Ns], z2 = zr[(f + 2) * Ns], z3 = zr[(f + 3) * Ns];
+          s += w0 * z0;
+          s += w1 * z1;
+          s += w2 * z2;
+          s += w3 * z3;
+        }
+        for (; f < F; ++f) s += wr[f] * zr[f * Ns];
+      }
+      yt[n] = dense_gnn_act<T>(s, act);
+    }
+  };
+
   for (int i = tid; i < N4 * Ns; i += 1024) {
     const int m = i / Ns, n = i - m * Ns;
     S[i] = (m < N && n < N) ? Sd[(size_t)m * N + n] : T(0);
   }
   for (int i = tid; i < KC4 * Ns; i += 1024) Z[i] = T(0);
   for (int i = tid; i < 3 * Ns; i += 1024) zrow[i] = T(0);
+  if (MODE == FWD_GNN) {
+    for (int i = tid; i <= NC * F; i += 1024) hw[i] = i < NC * F ? head_w[i] : (head_b ? head_b[0] : T(0));
+    for (int i = tid; i < (NC > K ? NC - K : 0) * F4 * Ns; i += 1024) ZX[i] = T(0);
+  }
   if (MODE == FWD_NODE)
     for (int i = tid; i < NC * (F + 1); i += 1024) {
       const int o = i / (F + 1), f = i - o * (F + 1);
@@ -154,6 +218,14 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
       }
       __syncthreads();
     }
+    if (MODE == FWD_GNN && t > 0) {
+      // the levels of h_{t-1} beyond the cell's own, state rows only (NC <= K: none, and no barrier is added to the step)
+      for (int k = K; k < NC; ++k) {
+        gnn_state_hop(k);
+        __syncthreads();
+      }
+      gnn_head(t - 1);
+    }
     // ---- taps: pre = W Zflat (time gates scale the x- and h-columns of W)
     acc_t outv[MAXT];
 #pragma unroll
@@ -211,6 +283,15 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
   if (MODE == FWD_NODE) {
     __syncthreads();                    // the last state is in Z
     node_head(Tn - 1);
+  }
+  if (MODE == FWD_GNN) {
+    // the last state has no next step whose hops would shift it: its NC - 1 levels are made here, state rows only
+    __syncthreads();                    // the last state is in Z
+    for (int k = 1; k < NC; ++k) {
+      gnn_state_hop(k);
+      __syncthreads();
+    }
+    gnn_head(Tn - 1);
   }
   if (MODE == FWD_LAST && head_w) {
     // ---- read-out on the last state (rows G .. G+F-1 of Z): logits[b][c] = head_w[c] . vec_{F,N}(h_T) + head_b[c].
@@ -583,6 +664,14 @@ size_t dense_bwd_lds(int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, 
 template <typename T>
 size_t dense_node_head_lds(int64_t F, int64_t O) { return sizeof(T) * (size_t)O * (size_t)(F + 1); }
 
+// what the graph-filter head adds to the forward image: head_w [K_o][F] and the bias (rounded up to four values), and the state rows
+// [F4][Ns] of each hop level the cell does not compute itself (K_o > K)
+template <typename T>
+size_t dense_gnn_head_lds(int64_t N, int64_t F, int64_t K, int64_t Ko) {
+  const size_t F4 = (size_t)((F + 3) & ~(int64_t)3), Ns = (size_t)lds_stride<T>((int)N);
+  return sizeof(T) * ((size_t)((Ko * F + 1 + 3) & ~(int64_t)3) + (Ko > K ? (size_t)(Ko - K) * F4 * Ns : 0));
+}
+
 constexpr size_t DENSE_LDS_MAX = 160 * 1024;
 
 template <typename T>
@@ -630,6 +719,7 @@ struct DenseFwdArgs {
   void* out = nullptr;
   int64_t NC = 0;
   int store = GCRNN_SMALL_STATES_ALL;
+  int act = 0;                     // FWD_GNN: head_w [NC][F] the head's taps, head_b [1], out = Y [B][T][1][N], NC = K_o
 };
 
 // One BPTT launch. The upstream gradient: dH [B][T][F][N]; or dlogits [B][NC] with head_w [NC][F N] (read-out on the last state); or
@@ -655,9 +745,11 @@ static bool dense_bt_ok(int64_t B, int64_t T) { return B > 0 && T > 0 && B <= 21
 template <typename T>
 static int dense_fwd_launch(const DenseFwdArgs& a, int mode) {
   const int64_t N = a.N, F = a.F, K = a.Kin > a.Kst ? a.Kin : a.Kst;
-  const size_t lds = dense_fwd_lds<T>(N, a.G, F, K) + (mode == FWD_NODE ? dense_node_head_lds<T>(F, a.NC) : 0);
+  const size_t lds = dense_fwd_lds<T>(N, a.G, F, K) + (mode == FWD_NODE ? dense_node_head_lds<T>(F, a.NC) : 0) +
+                     (mode == FWD_GNN ? dense_gnn_head_lds<T>(N, F, K, a.NC) : 0);
   const int64_t ot = ((F + 15) / 16) * ((N + 15) / 16);             // output tiles per step, dealt over 16 waves
-  auto kern = mode == FWD_NODE ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_NODE> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_NODE> : small_dense_fwd_kernel<T, 4, FWD_NODE>))
+  auto kern = mode == FWD_GNN ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_GNN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_GNN> : small_dense_fwd_kernel<T, 4, FWD_GNN>))
+              : mode == FWD_NODE ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_NODE> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_NODE> : small_dense_fwd_kernel<T, 4, FWD_NODE>))
               : mode == FWD_LAST ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_LAST> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_LAST> : small_dense_fwd_kernel<T, 4, FWD_LAST>))
                                  : (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_PLAIN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_PLAIN> : small_dense_fwd_kernel<T, 4, FWD_PLAIN>));
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -665,12 +757,12 @@ static int dense_fwd_launch(const DenseFwdArgs& a, int mode) {
   GCRNN_PRE_LAUNCH();
   kern<<<(unsigned)a.B, 1024, lds, a.st>>>((const T*)a.X, (const T*)a.h0, (const T*)a.wA, (const T*)a.wB, (const T*)a.bias, (const T*)a.gi,
                                           (const T*)a.gf, (const T*)a.Sd, (T*)a.H, (int)a.T, (int)N, (int)a.G, (int)F, (int)a.Kin, (int)a.Kst,
-                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.head_w, (const T*)a.head_b, (T*)a.out, (int)a.NC, a.store);
+                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.head_w, (const T*)a.head_b, (T*)a.out, (int)a.NC, a.store, a.act);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
 
-// The one place that picks the forward instantiation: <T> here, MAXT and the mode (FWD_PLAIN / FWD_LAST / FWD_NODE) in the launcher.
+// The one place that picks the forward instantiation: <T> here, MAXT and the mode (FWD_PLAIN / FWD_LAST / FWD_NODE / FWD_GNN) in the launcher.
 static int dense_fwd_run(int dtype, const DenseFwdArgs& a, int mode) {
   return dtype == GCRNN_F32 ? dense_fwd_launch<float>(a, mode) : dense_fwd_launch<double>(a, mode);
 }
@@ -852,4 +944,43 @@ extern "C" int gcrnn_small_dense_backward_node_head(int dtype, const void* X, co
                        .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n, .st = as_stream(stream), .dY = dY,
                        .head_w = node_w, .NC = O};
   return dense_bwd_run(dtype, a);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// one-layer graph-filter head on every state (the regression model's Selection-GNN head, GraphFilter(F -> 1, K_o) + activation): Y from
+// the forward launch; the backward is gcrnn_small_gnn_head_adjoint (gcrnn_small_gnn_head.hip) + gcrnn_small_dense_backward_node_head
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int gcrnn_small_dense_gnn_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t Ko,
+                                                    int backward, int gated, int dx) {
+  if (Ko <= 0 || Ko > GCRNN_SMALL_NODE_HEAD_MAX_OUT) return 0;
+  if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated)) return 0;
+  if (backward) {
+    // the BPTT launch takes the head's share as a per-node head of O = K_o outputs; the adjoint kernel's own image is S and eight rows
+    if (!gcrnn_small_dense_node_head_supported(dtype, N, G, F, Kin, Kst, Ko, 1, gated, dx)) return 0;
+    return (dtype == GCRNN_F32 ? gnn_adjoint_lds<float>(N) : gnn_adjoint_lds<double>(N)) <= DENSE_LDS_MAX ? 1 : 0;
+  }
+  const int64_t K = Kin > Kst ? Kin : Kst;
+  const size_t lds = dtype == GCRNN_F32 ? dense_fwd_lds<float>(N, G, F, K) + dense_gnn_head_lds<float>(N, F, K, Ko)
+                                        : dense_fwd_lds<double>(N, G, F, K) + dense_gnn_head_lds<double>(N, F, K, Ko);
+  return lds <= DENSE_LDS_MAX ? 1 : 0;
+}
+
+extern "C" int gcrnn_small_dense_forward_gnn_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB,
+                                                  const void* bias, const void* gi, const void* gf, const void* Sdense,
+                                                  const void* head_w, const void* head_b, void* H, void* Y, int64_t B, int64_t T,
+                                                  int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                                  int64_t gate_stride_t, int64_t gate_stride_n, int64_t Ko, int act, int store_states,
+                                                  void* stream) {
+  if (!X || !h0 || !wA || !wB || !Sdense || !head_w || !Y) return GCRNN_ERR_NULL_POINTER;
+  if (int s = dense_shared_status(gi, gf, false, nullptr, nullptr, true, dtype)) return s;
+  if (store_states != GCRNN_SMALL_STATES_ALL && store_states != GCRNN_SMALL_STATES_LAST && store_states != GCRNN_SMALL_STATES_NONE)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (store_states != GCRNN_SMALL_STATES_NONE && !H) return GCRNN_ERR_NULL_POINTER;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (Ko <= 0 || Ko > GCRNN_SMALL_NODE_HEAD_MAX_OUT || act < 0 || act > 3) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_gnn_head_supported(dtype, N, G, F, Kin, Kst, Ko, 0, gi != nullptr, 0)) return GCRNN_ERR_UNSUPPORTED;
+  const DenseFwdArgs a{.X = X, .h0 = h0, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .H = H, .B = B, .T = T, .N = N,
+                       .G = G, .F = F, .Kin = Kin, .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n,
+                       .st = as_stream(stream), .head_w = head_w, .head_b = head_b, .out = Y, .NC = Ko, .store = store_states, .act = act};
+  return dense_fwd_run(dtype, a, FWD_GNN);
 }

@@ -2993,21 +2993,23 @@ SMALL_STATES_ALL, SMALL_STATES_LAST, SMALL_STATES_NONE = 0, 1, 2      # gcrnn.h:
 def _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, head=None):
     """The one forward launch of the matrix-core family: the recurrence, the states `store` asks for and the output of `head`. head: None,
     ('last', head_w [C][F N], head_b [C] or None) -- the read-out on the last state, logits [B][C] -- or ('node', node_w [O][F], node_b [O] or
-    None) -- the per-node head on every state, Y [B][T][O][N]. Returns (H or None, logits / Y or None). Entry point: no head and every state
-    gcrnn_small_dense_forward; no head and the last state gcrnn_small_dense_forward_head without a read-out; 'last' the same entry with
-    one; 'node' gcrnn_small_dense_forward_node_head. Every operand stays a local of this frame up to the launch (_small_dense_bptt)."""
+    None) -- the per-node head on every state, Y [B][T][O][N] -- or ('gnn', head_w [K_o][F], head_b [1] or None, act) -- the one-layer
+    graph-filter head on every state, Y [B][T][1][N], act a key of _GFL_ACTS. Returns (H or None, logits / Y or None). Entry point: no head
+    and every state gcrnn_small_dense_forward; no head and the last state gcrnn_small_dense_forward_head without a read-out; 'last' the
+    same entry with one; 'node' gcrnn_small_dense_forward_node_head; 'gnn' gcrnn_small_dense_forward_gnn_head. Every operand stays a local
+    of this frame up to the launch (_small_dense_bptt)."""
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
     dt, dev = X.dtype, X.device
-    kind, hw, hb = head if head is not None else (None, None, None)
+    kind, hw, hb = head[:3] if head is not None else (None, None, None)
     assert head is not None or store != SMALL_STATES_NONE
     H = None if store == SMALL_STATES_NONE else torch.empty((B, T if store == SMALL_STATES_ALL else 1, F, N), dtype=dt, device=dev)
     out, NC = None, 0
     if head is not None:
         NC = hw.shape[0]
         assert tuple(hw.shape) == ((NC, F * N) if kind == 'last' else (NC, F)) and hw.dtype == dt
-        assert hb is None or (hb.dtype == dt and hb.numel() == NC)
-        out = torch.empty((B, NC) if kind == 'last' else (B, T, NC, N), dtype=dt, device=dev)
+        assert hb is None or (hb.dtype == dt and hb.numel() == (1 if kind == 'gnn' else NC))
+        out = torch.empty((B, NC) if kind == 'last' else (B, T, 1 if kind == 'gnn' else NC, N), dtype=dt, device=dev)
         hw = hw.detach().contiguous()
         hb = hb.detach().contiguous() if hb is not None else None
     bvec = bias.detach().contiguous().view(-1) if bias is not None else None
@@ -3023,8 +3025,8 @@ def _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, head=None):
         name = 'small_dense_forward'
         args += (_p(H),) + dims
     else:
-        name = 'small_dense_forward_node_head' if kind == 'node' else 'small_dense_forward_head'
-        args += (_p(hw), _p(hb), _p(H), _p(out)) + dims + (NC, store)
+        name = {'node': 'small_dense_forward_node_head', 'gnn': 'small_dense_forward_gnn_head'}.get(kind, 'small_dense_forward_head')
+        args += (_p(hw), _p(hb), _p(H), _p(out)) + dims + ((NC, _GFL_ACTS[head[3]], store) if kind == 'gnn' else (NC, store))
     check(getattr(lib, 'gcrnn_' + name)(*args, _stream()), name)
     return H, out
 
@@ -3306,6 +3308,93 @@ def small_cell_regress(X, h0, wA, wB, bias, graph, node_w, node_b, gi=None, gf=N
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
         return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('node', node_w, node_b))[1]
     return _SmallCellNodeHead.apply(X, h0, wA, wB, bias, gi, gf, node_w, node_b, graph)
+
+
+# ---- the regression model's Selection-GNN head on the matrix-core kernels: GraphFilter(F -> 1, K_o) + activation on every state inside the
+# forward launch; backward = the head's adjoint kernel + the per-node head's BPTT launch fed dU
+def small_gnn_head_supported(N, G, F, Kin, Kst, K_o, dtype, backward, gated, dx=False, E=1):
+    """The matrix-core small-graph kernels take this cell with a one-layer graph-filter head of K_o taps and one output feature on every
+    state (gcrnn_small_dense_gnn_head_supported; E = 1, fp32 / fp64; GCRNN_SMALL_GATHER=1 answers no, as for small_dense_supported).
+    backward: the training step, i.e. the forward launch with the head's LDS share, the adjoint kernel and the BPTT launch."""
+    if E != 1 or not small_dense_supported(N, G, F, Kin, Kst, dtype, backward, gated):
+        return False
+    shape = (dtype_code(dtype), int(N), int(G), int(F), int(Kin), int(Kst), int(K_o))
+    if not lib.gcrnn_small_dense_gnn_head_supported(*shape, 0, int(bool(gated)), 0):
+        return False
+    return not backward or bool(lib.gcrnn_small_dense_gnn_head_supported(*shape, 1, int(bool(gated)), int(bool(dx))))
+
+
+def small_gnn_head_adjoint(dY, Y, graph, K_o, act, out=None):
+    """dU [B][T][K_o][N] of the graph-filter head from dY and the stored Y, both [B][T][1][N]: dU_0 = dY . act'(Y), dU_k = dU_{k-1} S^T
+    (gcrnn_small_gnn_head_adjoint). out: a contiguous buffer to fill (every element is written), else a new one."""
+    B, T, _, N = Y.shape
+    dt = Y.dtype
+    dYc, Yc, Sd = dY.contiguous(), Y.contiguous(), graph.dense(dt)
+    assert dYc.dtype == dt and tuple(dYc.shape) == (B, T, 1, N)
+    dU = out if out is not None else torch.empty((B, T, K_o, N), dtype=dt, device=Y.device)
+    assert dU.is_contiguous() and dU.dtype == dt and tuple(dU.shape) == (B, T, K_o, N)
+    check(lib.gcrnn_small_gnn_head_adjoint(dtype_code(dt), _p(dYc), _p(Yc), _p(Sd), _p(dU), B * T, N, K_o, _GFL_ACTS[act], _stream()),
+          'small_gnn_head_adjoint')
+    return dU
+
+
+class _SmallCellGnnHead(torch.autograd.Function):
+    """Small-graph cell + GraphFilter(F -> 1, K_o) + activation on every state as ONE autograd node. Forward: one launch that stores every
+    state (BPTT reads them) and makes Y. Backward: the head's adjoint kernel (dU [B][T][K_o][N], K_o / F of a dH), then the per-node head's
+    BPTT launch with node_w = head_w and dY := dU (gcrnn_small_dense_backward_node_head forms dH_t = sum_k w_k (x) dU_k itself: no dH
+    [B][T][F][N] is allocated, written or read) and node_linear's backward kernel on (H, dU) for the head's own parameters."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph, act):
+        X, h0 = X.contiguous(), h0.contiguous()
+        H, Y = _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_ALL, ('gnn', head_w, head_b, act))
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, gi, gf, head_w, Y)
+        ctx.graph, ctx.has_hb, ctx.act = graph, head_b is not None, act
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, h0, H, wA, wB, bias, gi, gf, head_w, Y = ctx.saved_tensors
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        Ko = head_w.shape[0]
+        dt, dev = X.dtype, X.device
+        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_dx and not small_gnn_head_supported(N, G, F, Kin, Kst, Ko, dt, True, gi is not None, dx=True):
+            raise GcrnnError('small_cell_regress_gnn: no gradient for X at this shape (small_gnn_head_supported with dx)')
+        dU, hw = small_gnn_head_adjoint(dY.to(dt), Y, ctx.graph, Ko, ctx.act), head_w.detach().contiguous()
+        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dY', dU, hw))
+        # d head_w[k][f] = sum_{b,t,n} dU[b][t][k][n] H[b][t][f][n] and d head_b = sum dU_0: the per-node head's sums with O = K_o
+        dhw = dhb = None
+        want_hb = ctx.has_hb and ctx.needs_input_grad[8]
+        if (ctx.needs_input_grad[7] or want_hb) and node_linear_supported(F, Ko, dt):
+            nblk = int(lib.gcrnn_node_linear_blocks(B * T, N))
+            pw = torch.empty((nblk, Ko, F), dtype=dt, device=dev)
+            pnb = torch.empty((nblk, Ko), dtype=dt, device=dev)
+            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(H), _p(hw), _p(dU), None, _p(pw), _p(pnb), B * T, N, F, Ko, _stream()),
+                  'node_linear_backward')
+            dhw = pw.sum(dim=0) if ctx.needs_input_grad[7] else None
+            dhb = pnb[:, 0].sum(dim=0).view(1) if want_hb else None
+        else:
+            if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B T][K_o][F] its only temporary
+                dhw = torch.bmm(dU.view(B * T, Ko, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
+            dhb = dU[:, :, 0].sum().view(1) if want_hb else None
+        return grads + (dhw, dhb, None, None)
+
+
+def small_cell_regress_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, act=None, gi=None, gf=None):
+    """The small-graph cell followed by one graph-filter layer of K_o taps and one output feature on every state (head_w [K_o][F] =
+    GraphFilter.weight[0, 0], head_b [1] or None, the states' dtype; act in (None, 'relu', 'tanh', 'sigmoid')):
+    Y[b][t][0] = act(sum_k head_w[k] (h_t S^k) + head_b), [B][T][1][N] -- the values ops.graph_filter_layer gives on the cell's H, in
+    another summation order. Where nothing wants a gradient it is one launch that stores no state; otherwise one autograd node
+    (_SmallCellGnnHead) with gradients for X (only where wanted: small_gnn_head_supported with dx), h0, the taps, the bias, the gates and
+    the head. Shapes: small_gnn_head_supported."""
+    assert act in _GFL_ACTS, act
+    require_device(X, h0, wA, wB, bias, head_w)
+    operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
+        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('gnn', head_w, head_b, act))[1]
+    return _SmallCellGnnHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph, act)
 
 
 def small_gates_supported(N, G, F, Kin, Kst, dtype, backward):

@@ -837,6 +837,36 @@ int gcrnn_small_dense_backward_node_head(int dtype, const void* X, const void* h
                                          int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t O,
                                          void* stream);
 
+/* The forward kernel with a one-layer graph-filter head on EVERY state (the regression model's Selection-GNN head with
+ * dimNodeSignals = [F, 1], nFilterTaps = [K_o], NoPool and no MLP, reference architectures.py:1588-1604 and 1630-1632).
+ *   head_w [K_o][F] (GraphFilter.weight[0, 0]), head_b [1] or NULL, Y [B][T][1][N], all of `dtype`; act in the layer's codes
+ *   (0 identity, 1 ReLU -- a NaN stays a NaN --, 2 tanh, 3 sigmoid):
+ *     Y[b][t][0][n] = act( head_b + sum_{k < K_o} sum_f head_w[k][f] (h_t S^k)[f][n] )      (from head_b, k ascending, f ascending)
+ *   computed by the forward launch from the state rows of the hop levels of step t + 1 while they sit in LDS, so y_t reads nothing of
+ *   x_{t+1}; the levels beyond max(Kin, Kst) are shifted for the state rows alone, and the last state's levels after the time loop.
+ *   One thread per node, fixed order, no atomics: two runs give the same bits. store_states as above: _ALL for the training forward
+ *   (H bit-identical to gcrnn_small_dense_forward), _NONE for inference (H may be NULL: no state is ever stored), _LAST H [B][1][F][N].
+ * gcrnn_small_gnn_head_adjoint: the head's backward up to the state gradient, from dY and the stored Y, both [items][N], items = B T:
+ *     dz = dY . act'(Y),   dU [items][K_o][N]:  dU_0 = dz,  dU_k[m] = sum_n dU_{k-1}[n] Sdense[m][n]      (n ascending)
+ *   one wave per item, no atomics, every element of dU written. The caller then runs gcrnn_small_dense_backward_node_head with
+ *   node_w = head_w, O = K_o, dY = dU (dH_t = sum_k head_w[k] (x) dU_k is formed inside the BPTT launch; no dH exists) and
+ *   gcrnn_node_linear_backward with dh = NULL on (H, dU) for d head_w [K_o][F] and d head_b = its slot sums of dU_0.
+ * gcrnn_small_dense_gnn_head_supported: 1 <= K_o <= GCRNN_SMALL_NODE_HEAD_MAX_OUT and gcrnn_small_dense_supported(dtype, N, G, F, Kin,
+ *   Kst, backward, gated); backward = 0 also asks that the forward's LDS image with the head's K_o F + 1 values and, where
+ *   K_o > max(Kin, Kst), the extra levels' state rows fits; backward = 1 asks gcrnn_small_dense_node_head_supported(..., K_o, 1, gated,
+ *   dx) and the adjoint kernel's image (a training step asks both). Answers without a device.
+ * Checked before any launch, in this order: GCRNN_ERR_NULL_POINTER, GCRNN_ERR_BAD_DTYPE, GCRNN_ERR_BAD_SHAPE (also an unknown
+ * store_states or act, K_o <= 0 and K_o above the maximum), GCRNN_ERR_UNSUPPORTED where the query says no. */
+int gcrnn_small_dense_gnn_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t K_o,
+                                         int backward, int gated, int dx);
+int gcrnn_small_dense_forward_gnn_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                                       const void* gi, const void* gf, const void* Sdense, const void* head_w, const void* head_b,
+                                       void* H, void* Y, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                       int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t K_o,
+                                       int act, int store_states, void* stream);
+int gcrnn_small_gnn_head_adjoint(int dtype, const void* dY, const void* Y, const void* Sdense, void* dU, int64_t items, int64_t N,
+                                 int64_t K_o, int act, void* stream);
+
 /* Time gates of the small-graph regime (GGCRNNCell time gating, graphML.py:2248-2278, 2357-2374), both gates in one launch:
  *   gate[g][t][b] = sigmoid( lw_g . vec_{F,N}( tanh(A_g(S) x_t + B_g(S) h0 + 2 b_g) ) + lb_g ),  g = 0 input, 1 forget.
  * Parameters stacked over the two gates: wA2 [2][F][Kin][G], wB2 [2][F][Kst][F], bias2 [2][F] or NULL, lw2 [2][F*N]
