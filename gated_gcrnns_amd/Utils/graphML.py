@@ -719,10 +719,49 @@ class GGCRNNCell(nn.Module):
             return ops.small_edge_cell_train(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, gi, gf)
         return ops.small_edge_cell_forward(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, att_in, att_f, gi, gf, last_only=last_only)
 
-    def _small_gates(self, X, h0, train=False):
+    @staticmethod
+    def _small_node_gates_pays(X, train, head):
+        """Where the one-launch node gates are no slower than the composed batched pass (the acceptance rule of DESIGN 4.11 / 4.12, new
+        median <= off median x (1 + off spread), on tools/small_node_gates_bench.py's 72 rows, DESIGN 4.15: adj59 K = 4 and SBM 80 K = 5,
+        F = 20, node and time+node, fp32 / fp64, T = 5 / 20 / 200). 68 rows pass: every training step (1.03x .. 2.1x), every model
+        inference (head inside the launches, 1.09x .. 3.8x), every fp64 row and every row at T <= 20. The four that fail are the bare cell's
+        fp32 inference at T = 200, which stores every state, this path / the switched-off path in ms: adj59 2.359 / 2.182 and (time+node)
+        3.156 / 3.031, SBM 80 4.116 / 3.938 and 5.392 / 5.271 -- two latency-bound launches in a row (64 workgroups of gates, then the
+        recurrence) against batched passes that fill the chip at that length. Those rows are taken off the dispatch here; nothing between
+        T = 20 and T = 200 was measured, so fp32 cell inference keeps the composed pass from T = 21 up. GCRNN_SMALL_NODE_GATES=all takes them
+        all the same (peak memory 67 against 251 MB and 90 against 422 MB, 7 device events against 35 / 41). train: a backward may follow;
+        head: called for a head inside the launches (_small_head_route)."""
+        return train or head or X.dtype != torch.float32 or X.shape[1] <= 20
+
+    def _use_small_node_gates(self, X, train, head):
+        """Node gates of a cell on the small matrix-core path in one launch forward, one backward (ops.small_node_gates):
+        E = 1, every gate parameter in the input's dtype, shapes by ops.small_node_gates_supported, rows by _small_node_gates_pays
+        (GCRNN_SMALL_NODE_GATES=all: every supported row). GCRNN_NO_SMALL_NODE_GATES=1 switches back to the composed batched pass
+        (A/B). Both variables are read at every call."""
+        if os.environ.get('GCRNN_NO_SMALL_NODE_GATES') or self.E != 1 or not self._sigma_is_tanh():
+            return False
+        subs = (self.GRNN_node_in, self.GRNN_node_forget, self.GFL_node_in[0], self.GFL_node_forget[0])
+        if any(p.dtype != X.dtype for m in subs for p in m.parameters()):
+            return False
+        if os.environ.get('GCRNN_SMALL_NODE_GATES') != 'all' and not self._small_node_gates_pays(X, train, head):
+            return False
+        return ops.small_node_gates_supported(self.N, self.G, self.F, self.Kin, self.Kst, X.dtype, backward=train)
+
+    def _small_gates(self, X, h0, train=False, head=False):
         """(gi, gf) as the one-launch recurrence takes them: None, [T][B] time gates, or [B][T][N] node gates (times the time gates)."""
         gi, gf = self._small_time_gates(X, h0, train)
-        if self.spatial_gating == 'node':
+        if self.spatial_gating == 'node' and self._use_small_node_gates(X, train, head):
+            # both node gates of every step in one launch (parameters stacked input | forget): gates [2][B][T][N]
+            sub_i, sub_f = self.GRNN_node_in, self.GRNN_node_forget
+            gfl_i, gfl_f = self.GFL_node_in[0], self.GFL_node_forget[0]
+            gates = ops.small_node_gates(
+                X, h0, torch.stack((sub_i.weight_A[:, 0], sub_f.weight_A[:, 0])), torch.stack((sub_i.weight_B[:, 0], sub_f.weight_B[:, 0])),
+                torch.stack((sub_i.bias.view(-1), sub_f.bias.view(-1))) if sub_i.bias is not None else None,
+                torch.stack((gfl_i.weight.reshape(self.Kst, self.F), gfl_f.weight.reshape(self.Kst, self.F))),
+                torch.stack((gfl_i.bias.view(()), gfl_f.bias.view(()))) if gfl_i.bias is not None else None, self.graph)
+            gi = gates[0] if gi is None else gates[0] * gi.t().unsqueeze(2)
+            gf = gates[1] if gf is None else gates[1] * gf.t().unsqueeze(2)
+        elif self.spatial_gating == 'node':
             # node gates (graphML.py:2379-2399) from one batched pass over all t; the recurrence takes them per node,
             # multiplied by the time gates when both are on: gates [B][T][N]
             B = X.shape[0]
@@ -785,7 +824,7 @@ class GGCRNNCell(nn.Module):
             return None
         assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
         ops.require_device(X, h0, self.weight_A)
-        return (backward,) + self._small_gates(X, h0, backward)
+        return (backward,) + self._small_gates(X, h0, backward, head=True)
 
     @staticmethod
     def _small_edge_head_pays(X, head_kind):

@@ -184,6 +184,10 @@ def _bind(lib):
         'gcrnn_small_gates_forward': (C.c_int, [C.c_int] + [_c_p] * 9 + [_c_i64] * 7 + [_c_p]),
         'gcrnn_small_gates_backward': (C.c_int, [C.c_int] + [_c_p] * 14 + [_c_i64] * 7 + [_c_p]),
         'gcrnn_small_gates_backward_dx': (C.c_int, [C.c_int] + [_c_p] * 15 + [_c_i64] * 7 + [_c_p]),
+        'gcrnn_small_node_gates_supported': (C.c_int, [C.c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, C.c_int]),
+        'gcrnn_small_node_gates_forward': (C.c_int, [C.c_int] + [_c_p] * 9 + [_c_i64] * 7 + [_c_p]),
+        'gcrnn_small_node_gates_backward': (C.c_int, [C.c_int] + [_c_p] * 14 + [_c_i64] * 7 + [_c_p]),
+        'gcrnn_small_node_gates_backward_dx': (C.c_int, [C.c_int] + [_c_p] * 15 + [_c_i64] * 7 + [_c_p]),
         'gcrnn_small_edge_supported': (C.c_int, [C.c_int] + [_c_i64] * 7),
         'gcrnn_small_edge_forward': (C.c_int, [C.c_int] + [_c_p] * 21 + [_c_i64] * 9 + [C.c_int, _c_p]),
         'gcrnn_small_edge_backward_supported': (C.c_int, [C.c_int] + [_c_i64] * 7),

@@ -8,6 +8,24 @@
 // One workgroup per (sequence, gate): grid (B, 2). Everything in LDS / registers, layouts and strides as in
 // gcrnn_small_mfma.hip. The backward kernel recomputes c_t, accumulates the parameter gradients of its sequence in registers
 // (tile-fragment layout) and emits per-sequence partial sums (added by the caller in a fixed order).
+//
+// Node gates (reference GGCRNNCell node gating, graphML.py:2379-2399): the same gate cell d_t = c_t, read out by an F -> 1 graph
+// filter in place of the Linear(F N -> 1):
+//   gate_t[n] = sigmoid( bf + sum_{k < Kst} sum_f wf[k][f] (d_t S^k)[f][n] )                per sequence, step and node
+// Same grid, prologue and step; d_t goes to LDS (Zh0, free after the prologue) and the filter is evaluated TAPS FIRST:
+//   u_k[n] = sum_f wf[k][f] d_t[f][n]  (four interleaved splits of f, f ascending in each, joined (s0 + s1) + (s2 + s3)),
+//   then Horner  u_k += u_{k+1} S  for k = Kst - 2 .. 0  (sixteen interleaved splits of m, m ascending in each, joined by a fixed
+//   tree of four cross-lane adds); the last level adds the bias and goes through the sigmoid straight to memory.
+// That is Kst - 1 products of an N-vector with S on the VALU (F times fewer multiply-adds than hopping d_t on the matrix cores, and
+// no F x N hop level to park). The step is a chain of short dependent phases, so each product is spread over the whole workgroup: a
+// wave owns 4 columns n and splits the sum over m sixteen ways. Its 32-lane LDS groups read 4 consecutive words of 8 rows of S; the
+// rows sit at stride Ns = 4 * odd words, so an fp32 read hits 32 distinct banks (fp64: at most 2-way) -- the layout lds_stride was made
+// for. The taps read 16 consecutive n of 4 rows of d_t. The backward pass needs the transposed products
+// du_k[m] = sum_n du_{k-1}[n] S[m][n] and dwf[k][f] = sum_n du_k[n] d_t[f][n]: 4 rows x 16 interleaved splits of n per wave (16
+// consecutive words of 2 rows per LDS group: at most 2-way), joined by the same tree.
+// No atomics anywhere: the order above is fixed, two runs give the same bits. The u_k / du_k rows live in Zh1 when Kst <= F4, so the
+// LDS image grows by the filter taps (and their gradient) only; otherwise by Kst rows more. The backward kernel takes
+// dl = d loss / d (pre-sigmoid value): the caller forms dgate . gate . (1 - gate), as for the time gates' dsum.
 #include "gcrnn_common.h"
 #include "gcrnn_small_mfma.h"
 
@@ -220,18 +238,123 @@ __global__ __launch_bounds__(1024) void small_gate_fwd_kernel(
   }
 }
 
+// LDS of the node read-out beyond the time gates' image, from `base`: the filter taps WF [Kst][F], in the backward pass their gradient
+// DWF [Kst][F], and the rows U [Kst][Ns] (u_k forward, du_k backward) -- Zh1 where they fit in it.
+template <typename T>
+struct NodeBufs { T *WF, *DWF, *U; };
+
+template <typename T>
+__device__ __forceinline__ NodeBufs<T> node_bufs(const GateCtx<T>& c, T* base, bool backward) {
+  NodeBufs<T> nb;
+  nb.WF = base;
+  nb.DWF = base + c.Kst * c.F;
+  nb.U = (c.Kst <= c.F4) ? c.Zh1 : base + (backward ? 2 : 1) * c.Kst * c.F;
+  return nb;
+}
+
+// sum over the 16 lanes of a wave that share (lane & 3), in a fixed tree; every one of them gets the sum
+template <typename T>
+__device__ __forceinline__ T sum16(T p) {
+  p += __shfl_xor(p, 4, 64);
+  p += __shfl_xor(p, 8, 64);
+  p += __shfl_xor(p, 16, 64);
+  p += __shfl_xor(p, 32, 64);
+  return p;
+}
+
+// the fragments of d_t (f < F, n < N) into the rows of Zh0
+template <typename T>
+__device__ __forceinline__ void node_put_d(const GateCtx<T>& c, const typename Mf<T>::acc (&cv)[GMAXT]) {
+#pragma unroll
+  for (int q = 0; q < GMAXT; ++q) {
+    const int tile = c.wave + q * 16;
+    if (tile >= c.tilesF * c.tilesN) break;
+    const int i0 = (tile / c.tilesN) << 4, j0 = (tile % c.tilesN) << 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int f = i0 + Mf<T>::row(c.lane, r), n = j0 + c.li;
+      if (f < c.F && n < c.N) c.Zh0[f * c.Ns + n] = cv[q][r];
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void small_node_gate_fwd_kernel(
+    const T* __restrict__ X,        // [B][Tn][G][N]
+    const T* __restrict__ h0,       // [B][F][N]
+    const T* __restrict__ wA2,      // [2][F][Kin][G]
+    const T* __restrict__ wB2,      // [2][F][Kst][F]
+    const T* __restrict__ bias2,    // [2][F] or null
+    const T* __restrict__ wf2,      // [2][Kst][F]
+    const T* __restrict__ bf2,      // [2] or null
+    const T* __restrict__ Sd,
+    T* __restrict__ gate,           // [2][B][Tn][N]
+    int Tn, int N, int G, int F, int Kin, int Kst, int B) {
+  typedef typename Mf<T>::acc acc_t;
+  extern __shared__ __attribute__((aligned(16))) char smem_gate[];
+  GateCtx<T> c;
+  c.N = N; c.G = G; c.F = F; c.Kin = Kin; c.Kst = Kst;
+  c.tid = threadIdx.x; c.lane = c.tid & 63; c.wave = c.tid >> 6; c.li = c.lane & 15; c.lk = c.lane >> 4;
+  const int b = blockIdx.x, g = blockIdx.y;
+  acc_t yb[GMAXT], cv[GMAXT];
+  gate_prologue<T>(c, smem_gate, Sd, h0 + (size_t)b * F * N, wA2 + (size_t)g * F * Kin * G, wB2 + (size_t)g * F * Kst * F,
+                   bias2 ? bias2 + (size_t)g * F : nullptr, yb);
+  const int Ns = c.Ns;
+  const NodeBufs<T> nb = node_bufs<T>(c, c.red + 64, false);
+  for (int i = c.tid; i < Kst * F; i += 1024) nb.WF[i] = wf2[(size_t)g * Kst * F + i];
+  const T bf = bf2 ? bf2[g] : T(0);
+  const int c4 = c.lane & 3, s16 = c.lane >> 2, nblk4 = (N + 3) >> 2;
+  T* gout = gate + ((size_t)g * B + b) * Tn * N;
+  __syncthreads();
+  for (int t = 0; t < Tn; ++t) {
+    gate_step<T>(c, X + ((size_t)b * Tn + t) * G * N, yb, cv);
+    node_put_d<T>(c, cv);
+    __syncthreads();
+    for (int it = c.wave; it < Kst * c.tilesN; it += 16) {           // u_k[n] = sum_f wf[k][f] d_t[f][n]: 16 columns x 4 splits of f
+      const int k = it / c.tilesN, n = ((it - k * c.tilesN) << 4) + c.li;
+      T p = T(0);
+      if (n < N)
+        for (int f = c.lk; f < F; f += 4) p += nb.WF[k * F + f] * c.Zh0[f * Ns + n];
+      p += __shfl_xor(p, 16, 64);
+      p += __shfl_xor(p, 32, 64);
+      if (c.lk == 0 && n < N) nb.U[k * Ns + n] = p;
+    }
+    __syncthreads();
+    for (int k = Kst - 2; k >= 0; --k) {                             // u_k += u_{k+1} S: 4 columns x 16 splits of m
+      const T* up = nb.U + (k + 1) * Ns;
+      for (int it = c.wave; it < nblk4; it += 16) {
+        const int n = (it << 2) + c4;
+        T p = T(0);
+        if (n < N)
+          for (int m = s16; m < N; m += 16) p += up[m] * c.S[m * Ns + n];
+        p = sum16<T>(p);
+        if (s16 == 0 && n < N) {
+          const T v = nb.U[k * Ns + n] + p;
+          if (k > 0) nb.U[k * Ns + n] = v;
+          else gout[(size_t)t * N + n] = sigmoid_t<T>(v + bf);       // the last level goes straight out
+        }
+      }
+      if (k > 0) __syncthreads();
+    }
+    if (Kst == 1 && c.tid < N) gout[(size_t)t * N + c.tid] = sigmoid_t<T>(nb.U[c.tid] + bf);
+  }
+}
+
 // DX = true also writes this gate's share of the input gradient, pdX[b][g][t] = sum_k (A_k^T dpre_t)(S^T)^k [G x N] (Horner, on
 // the matrix cores): the hop levels Zx of x_t are free once dA has consumed them, so levels 0 / 1 serve as the chain's
 // ping-pong accumulators (Kin = 1 has no hop and needs none) -- no LDS beyond the plain backward's.
-template <typename T, bool DX>
+// NODE = true is the node gates' read-out (the F -> 1 graph filter) in place of the Linear: lw2 is wf2 [2][Kst][F], dsum is
+// dl [2][B][Tn][N], plw is pwf [B][2][Kst][F], plb is pbf [B][2]. Only the way d pre-activation is formed from the upstream gradient
+// and the read-out's own gradients differ; from dpre on the two modes run the same code.
+template <typename T, bool DX, bool NODE>
 __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
     const T* __restrict__ X, const T* __restrict__ h0, const T* __restrict__ wA2, const T* __restrict__ wB2,
     const T* __restrict__ bias2, const T* __restrict__ lw2, const T* __restrict__ Sd,
-    const T* __restrict__ dsum,     // [2][Tn][B]: d loss / d (lw . c + lb)
+    const T* __restrict__ dsum,     // [2][Tn][B]: d loss / d (lw . c + lb); NODE: [2][B][Tn][N]
     T* __restrict__ pA,             // [B][2][F][Kin][G]
     T* __restrict__ pB,             // [B][2][F][Kst][F]
     T* __restrict__ pb,             // [B][2][F]
-    T* __restrict__ plw,            // [B][2][F*N]
+    T* __restrict__ plw,            // [B][2][F*N]; NODE: [B][2][Kst][F]
     T* __restrict__ plb,            // [B][2]
     T* __restrict__ pdh0,           // [B][2][F][N] or null
     T* __restrict__ pdX,            // [B][2][Tn][G][N] (DX)
@@ -250,12 +373,18 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
   T* dP = c.red + 64;                               // [F4][Ns] d pre-activation of the current step (A operand of dA)
   T* dY = dP + (size_t)c.F4 * Ns;                   // [F4][Ns] sum over t of it (= d Yb), filled at the end
   for (int i = c.tid; i < 2 * c.F4 * Ns; i += 1024) dP[i] = T(0);
+  const NodeBufs<T> nb = node_bufs<T>(c, dY + (size_t)c.F4 * Ns, true);
+  if (NODE)
+    for (int i = c.tid; i < Kst * F; i += 1024) {
+      nb.WF[i] = lw2[(size_t)g * Kst * F + i];
+      nb.DWF[i] = T(0);
+    }
   const T* lw = lw2 + (size_t)g * F * N;
 #pragma unroll
   for (int q = 0; q < GMAXT; ++q) {
     lwv[q] = dlw[q] = dyb[q] = acc_t{0, 0, 0, 0};
     const int tile = c.wave + q * 16;
-    if (tile >= c.tilesF * c.tilesN) break;
+    if (NODE || tile >= c.tilesF * c.tilesN) break;
     const int i0 = (tile / c.tilesN) << 4, j0 = (tile % c.tilesN) << 4;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -263,6 +392,8 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
       if (f < F && n < N) lwv[q][r] = lw[(size_t)f * N + n];
     }
   }
+  const int r4 = c.lane & 3, s16 = c.lane >> 2;                     // NODE: 4 rows x 16 interleaved splits of the columns per wave
+  const int nblk4 = (N + 3) >> 2, fblk4 = c.F4 >> 2;
   // dA tiles [F x Kin G4]: tile id = fi * tilesKG + kj, persistent over t on waves 0 .. tilesF * tilesKG - 1 (<= 16 checked)
   const int tilesKG = (c.KG4 + 15) >> 4;
   acc_t dA = {0, 0, 0, 0};
@@ -270,7 +401,38 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
   __syncthreads();
   for (int t = 0; t < Tn; ++t) {
     gate_step<T>(c, X + ((size_t)b * Tn + t) * G * N, yb, cv);
-    const T ds = dsum[((size_t)g * Tn + t) * B + b];
+    T ds = T(0);
+    if (NODE) {
+      node_put_d<T>(c, cv);
+      if (c.tid < N) {
+        ds = dsum[(((size_t)g * B + b) * Tn + t) * N + c.tid];        // du_0 = dl_t; this thread's share of dbf
+        nb.U[c.tid] = ds;
+      }
+      __syncthreads();
+      for (int k = 1; k < Kst; ++k) {                                // du_k[m] = sum_n du_{k-1}[n] S[m][n]
+        const T* up = nb.U + (k - 1) * Ns;
+        for (int it = c.wave; it < nblk4; it += 16) {
+          const int m = (it << 2) + r4;
+          T p = T(0);
+          if (m < N)
+            for (int n = s16; n < N; n += 16) p += up[n] * c.S[m * Ns + n];
+          p = sum16<T>(p);
+          if (s16 == 0 && m < N) nb.U[k * Ns + m] = p;
+        }
+        __syncthreads();
+      }
+      for (int it = c.wave; it < Kst * fblk4; it += 16) {            // dwf[k][f] += sum_n du_k[n] d_t[f][n]
+        const int k = it / fblk4, f = ((it - k * fblk4) << 2) + r4;
+        const T* up = nb.U + k * Ns;
+        T p = T(0);
+        if (f < F)
+          for (int n = s16; n < N; n += 16) p += up[n] * c.Zh0[f * Ns + n];
+        p = sum16<T>(p);
+        if (s16 == 0 && f < F) nb.DWF[k * F + f] += p;               // the same thread owns (k, f) at every step
+      }
+    } else {
+      ds = dsum[((size_t)g * Tn + t) * B + b];
+    }
     dlb += ds;
 #pragma unroll
     for (int q = 0; q < GMAXT; ++q) {
@@ -280,10 +442,18 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const T cc = cv[q][r];
-        dlw[q][r] += ds * cc;
-        const T dp = ds * lwv[q][r] * (T(1) - cc * cc);            // lwv is zero on padded entries
-        dyb[q][r] += dp;
         const int f = i0 + Mf<T>::row(c.lane, r), n = j0 + c.li;
+        T dp;
+        if (NODE) {
+          T dd = T(0);                                               // dd = sum_k wf[k][f] du_k[n], k ascending; zero on padded entries
+          if (f < F && n < N)
+            for (int k = 0; k < Kst; ++k) dd += nb.WF[k * F + f] * nb.U[k * Ns + n];
+          dp = (f < F && n < N) ? dd * (T(1) - cc * cc) : T(0);
+        } else {
+          dlw[q][r] += ds * cc;
+          dp = ds * lwv[q][r] * (T(1) - cc * cc);                    // lwv is zero on padded entries
+        }
+        dyb[q][r] += dp;
         if (f < F && n < N) dP[f * Ns + n] = dp;
       }
     }
@@ -337,7 +507,13 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
     }
   }
   // ---- per-sequence results
-  if (c.tid == 0) plb[(size_t)b * 2 + g] = dlb;
+  if (NODE) {
+    const T s = block_sum<T>(c, dlb);                                // dbf = sum over t and n of dl (thread n holds its sum over t)
+    if (c.tid == 0) plb[(size_t)b * 2 + g] = s;
+    for (int i = c.tid; i < Kst * F; i += 1024) plw[((size_t)b * 2 + g) * Kst * F + i] = nb.DWF[i];
+  } else if (c.tid == 0) {
+    plb[(size_t)b * 2 + g] = dlb;
+  }
 #pragma unroll
   for (int q = 0; q < GMAXT; ++q) {
     const int tile = c.wave + q * 16;
@@ -347,7 +523,7 @@ __global__ __launch_bounds__(1024) void small_gate_bwd_kernel(
     for (int r = 0; r < 4; ++r) {
       const int f = i0 + Mf<T>::row(c.lane, r), n = j0 + c.li;
       if (f < F && n < N) {
-        plw[((size_t)b * 2 + g) * F * N + (size_t)f * N + n] = dlw[q][r];
+        if (!NODE) plw[((size_t)b * 2 + g) * F * N + (size_t)f * N + n] = dlw[q][r];
         dY[f * Ns + n] = dyb[q][r];
       }
     }
@@ -500,7 +676,7 @@ static int gates_bwd_launch(const void* X, const void* h0, const void* wA2, cons
                             void* pdX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
                             hipStream_t st) {
   const size_t lds = gate_lds<T>(N, G, F, Kin, true);
-  auto kern = small_gate_bwd_kernel<T, DX>;
+  auto kern = small_gate_bwd_kernel<T, DX, false>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return GCRNN_ERR_LAUNCH;
   GCRNN_PRE_LAUNCH();
@@ -542,4 +718,114 @@ extern "C" int gcrnn_small_gates_backward_dx(int dtype, const void* X, const voi
                                          Kin, Kst, as_stream(stream));
   return gates_bwd_launch<double, true>(X, h0, wA2, wB2, bias2, lw2, Sdense, dsum, pA, pB, pb, plw, plb, pdh0, pdX, B, T, N, G, F,
                                         Kin, Kst, as_stream(stream));
+}
+
+// ---------------------------------------------------------------------------------------------------------------- node gates
+namespace {
+
+// the time gates' image plus the filter taps (and, backward, their gradient) and, where Kst > F4, the Kst rows that Zh1 cannot hold
+template <typename T>
+size_t node_gate_lds(int64_t N, int64_t F, int64_t G, int64_t Kin, int64_t Kst, bool backward) {
+  const int Ns = lds_stride<T>((int)N), F4 = ((int)F + 3) & ~3;
+  size_t e = (size_t)Kst * F * (backward ? 2 : 1);
+  if (Kst > F4) e += (size_t)Kst * Ns;
+  return gate_lds<T>(N, G, F, Kin, backward) + sizeof(T) * e;
+}
+
+template <typename T>
+bool node_gate_supported(int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, bool backward) {
+  return gate_supported<T>(N, G, F, Kin, Kst, backward) && node_gate_lds<T>(N, F, G, Kin, Kst, backward) <= 160 * 1024;
+}
+
+template <typename T>
+int node_gates_fwd_launch(const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2, const void* wf2,
+                          const void* bf2, const void* Sd, void* gate, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F,
+                          int64_t Kin, int64_t Kst, hipStream_t st) {
+  const size_t lds = node_gate_lds<T>(N, F, G, Kin, Kst, false);
+  auto kern = small_node_gate_fwd_kernel<T>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return GCRNN_ERR_LAUNCH;
+  GCRNN_PRE_LAUNCH();
+  kern<<<dim3((unsigned)B, 2), 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)wA2, (const T*)wB2, (const T*)bias2,
+                                                (const T*)wf2, (const T*)bf2, (const T*)Sd, (T*)gate, (int)Tn, (int)N, (int)G,
+                                                (int)F, (int)Kin, (int)Kst, (int)B);
+  GCRNN_CHECK_LAUNCH();
+  return GCRNN_OK;
+}
+
+template <typename T, bool DX>
+int node_gates_bwd_launch(const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2, const void* wf2,
+                          const void* Sd, const void* dl, void* pA, void* pB, void* pb, void* pwf, void* pbf, void* pdh0,
+                          void* pdX, int64_t B, int64_t Tn, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                          hipStream_t st) {
+  const size_t lds = node_gate_lds<T>(N, F, G, Kin, Kst, true);
+  auto kern = small_gate_bwd_kernel<T, DX, true>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return GCRNN_ERR_LAUNCH;
+  GCRNN_PRE_LAUNCH();
+  kern<<<dim3((unsigned)B, 2), 1024, lds, st>>>((const T*)X, (const T*)h0, (const T*)wA2, (const T*)wB2, (const T*)bias2,
+                                                (const T*)wf2, (const T*)Sd, (const T*)dl, (T*)pA, (T*)pB, (T*)pb, (T*)pwf,
+                                                (T*)pbf, (T*)pdh0, (T*)pdX, (int)Tn, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
+                                                (int)B);
+  GCRNN_CHECK_LAUNCH();
+  return GCRNN_OK;
+}
+
+// the checks the three entry points share, after their NULL tests
+int node_gates_check(int dtype, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int backward) {
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return GCRNN_ERR_BAD_DTYPE;
+  if (B <= 0 || T <= 0 || B > 65535 * 32768LL || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_node_gates_supported(dtype, N, G, F, Kin, Kst, backward)) return GCRNN_ERR_UNSUPPORTED;
+  return GCRNN_OK;
+}
+
+}  // namespace
+
+extern "C" int gcrnn_small_node_gates_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int backward) {
+  if (dtype != GCRNN_F32 && dtype != GCRNN_F64) return 0;
+  const bool own = dtype == GCRNN_F32 ? node_gate_supported<float>(N, G, F, Kin, Kst, backward != 0)
+                                      : node_gate_supported<double>(N, G, F, Kin, Kst, backward != 0);
+  return own && gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward != 0, 1) ? 1 : 0;
+}
+
+extern "C" int gcrnn_small_node_gates_forward(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2,
+                                              const void* bias2, const void* wf2, const void* bf2, const void* Sdense, void* gate,
+                                              int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                              void* stream) {
+  if (!X || !h0 || !wA2 || !wB2 || !wf2 || !Sdense || !gate) return GCRNN_ERR_NULL_POINTER;
+  const int rc = node_gates_check(dtype, B, T, N, G, F, Kin, Kst, 0);
+  if (rc != GCRNN_OK) return rc;
+  if (dtype == GCRNN_F32)
+    return node_gates_fwd_launch<float>(X, h0, wA2, wB2, bias2, wf2, bf2, Sdense, gate, B, T, N, G, F, Kin, Kst, as_stream(stream));
+  return node_gates_fwd_launch<double>(X, h0, wA2, wB2, bias2, wf2, bf2, Sdense, gate, B, T, N, G, F, Kin, Kst, as_stream(stream));
+}
+
+extern "C" int gcrnn_small_node_gates_backward(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2,
+                                               const void* bias2, const void* wf2, const void* Sdense, const void* dl, void* pA,
+                                               void* pB, void* pb, void* pwf, void* pbf, void* pdh0, int64_t B, int64_t T,
+                                               int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, void* stream) {
+  if (!X || !h0 || !wA2 || !wB2 || !wf2 || !Sdense || !dl || !pA || !pB || !pb || !pwf || !pbf) return GCRNN_ERR_NULL_POINTER;
+  const int rc = node_gates_check(dtype, B, T, N, G, F, Kin, Kst, 1);
+  if (rc != GCRNN_OK) return rc;
+  if (dtype == GCRNN_F32)
+    return node_gates_bwd_launch<float, false>(X, h0, wA2, wB2, bias2, wf2, Sdense, dl, pA, pB, pb, pwf, pbf, pdh0, nullptr, B, T, N,
+                                               G, F, Kin, Kst, as_stream(stream));
+  return node_gates_bwd_launch<double, false>(X, h0, wA2, wB2, bias2, wf2, Sdense, dl, pA, pB, pb, pwf, pbf, pdh0, nullptr, B, T, N,
+                                              G, F, Kin, Kst, as_stream(stream));
+}
+
+extern "C" int gcrnn_small_node_gates_backward_dx(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2,
+                                                  const void* bias2, const void* wf2, const void* Sdense, const void* dl, void* pA,
+                                                  void* pB, void* pb, void* pwf, void* pbf, void* pdh0, void* pdX, int64_t B,
+                                                  int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                                  void* stream) {
+  if (!X || !h0 || !wA2 || !wB2 || !wf2 || !Sdense || !dl || !pA || !pB || !pb || !pwf || !pbf || !pdX)
+    return GCRNN_ERR_NULL_POINTER;
+  const int rc = node_gates_check(dtype, B, T, N, G, F, Kin, Kst, 1);
+  if (rc != GCRNN_OK) return rc;
+  if (dtype == GCRNN_F32)
+    return node_gates_bwd_launch<float, true>(X, h0, wA2, wB2, bias2, wf2, Sdense, dl, pA, pB, pb, pwf, pbf, pdh0, pdX, B, T, N, G,
+                                              F, Kin, Kst, as_stream(stream));
+  return node_gates_bwd_launch<double, true>(X, h0, wA2, wB2, bias2, wf2, Sdense, dl, pA, pB, pb, pwf, pbf, pdh0, pdX, B, T, N, G, F,
+                                             Kin, Kst, as_stream(stream));
 }

@@ -3450,6 +3450,65 @@ def small_time_gates(X, h0, wA2, wB2, bias2, lw2, lb2, graph):
     return _SmallTimeGates.apply(X, h0, wA2, wB2, bias2, lw2, lb2, graph)
 
 
+def small_node_gates_supported(N, G, F, Kin, Kst, dtype, backward):
+    """Both node gates of a small-graph cell in one launch (gcrnn_small_node_gates_supported, which implies small_dense_supported with
+    gates; GCRNN_SMALL_GATHER=1 answers no, as for small_gates_supported). backward: the backward launch too, with or without dX."""
+    if dtype not in (torch.float32, torch.float64) or os.environ.get('GCRNN_SMALL_GATHER'):
+        return False
+    return bool(lib.gcrnn_small_node_gates_supported(dtype_code(dtype), int(N), int(G), int(F), int(Kin), int(Kst), int(backward)))
+
+
+class _SmallNodeGates(torch.autograd.Function):
+    """Both node gates of a small-graph cell for all steps: one launch forward, one backward (reference graphML.py:2379-2399).
+    Parameters stacked over (input, forget); wf2 [2][Kst][F] / bf2 [2] are the F -> 1 graph filters. Returns gates [2][B][T][N]. The
+    backward kernel takes the gradient at the pre-sigmoid value, formed here from the saved gates; the gradient for X comes from its dx
+    variant, only when X wants one. The per-sequence partial sums are added over B (and the two gates' shares of dX / dh0) by torch's
+    deterministic reductions, in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA2, wB2, bias2, wf2, bf2, graph):
+        X, h0, wA2, wB2, wf2 = X.contiguous(), h0.contiguous(), wA2.contiguous(), wB2.contiguous(), wf2.contiguous()
+        bias2 = bias2.contiguous() if bias2 is not None else None
+        bf2 = bf2.contiguous() if bf2 is not None else None
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA2.shape[1], wA2.shape[2], wB2.shape[2]
+        Sd = graph.dense(X.dtype)
+        gates = torch.empty((2, B, T, N), dtype=X.dtype, device=X.device)
+        check(lib.gcrnn_small_node_gates_forward(dtype_code(X.dtype), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(wf2), _p(bf2),
+                                                 _p(Sd), _p(gates), B, T, N, G, F, Kin, Kst, _stream()), 'small_node_gates_forward')
+        ctx.save_for_backward(X, h0, wA2, wB2, bias2, wf2, gates)
+        ctx.graph, ctx.has_bf = graph, bf2 is not None
+        return gates
+
+    @staticmethod
+    def backward(ctx, dgates):
+        X, h0, wA2, wB2, bias2, wf2, gates = ctx.saved_tensors
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA2.shape[1], wA2.shape[2], wB2.shape[2]
+        dt, dev = X.dtype, X.device
+        dl = (dgates * gates * (1 - gates)).contiguous()                      # through the sigmoid
+        Sd = ctx.graph.dense(dt)
+        pA = torch.empty((B, 2, F, Kin, G), dtype=dt, device=dev)
+        pB = torch.empty((B, 2, F, Kst, F), dtype=dt, device=dev)
+        pb = torch.empty((B, 2, F), dtype=dt, device=dev)
+        pwf = torch.empty((B, 2, Kst, F), dtype=dt, device=dev)
+        pbf = torch.empty((B, 2), dtype=dt, device=dev)
+        pdh0 = torch.empty((B, 2, F, N), dtype=dt, device=dev) if ctx.needs_input_grad[1] else None
+        pdX = torch.empty((B, 2, T, G, N), dtype=dt, device=dev) if ctx.needs_input_grad[0] else None
+        name = 'small_node_gates_backward_dx' if pdX is not None else 'small_node_gates_backward'
+        args = (dtype_code(dt), _p(X), _p(h0), _p(wA2), _p(wB2), _p(bias2), _p(wf2), _p(Sd), _p(dl), _p(pA), _p(pB), _p(pb), _p(pwf),
+                _p(pbf), _p(pdh0))
+        check(getattr(lib, 'gcrnn_' + name)(*args, *((_p(pdX),) if pdX is not None else ()), B, T, N, G, F, Kin, Kst, _stream()), name)
+        return (pdX[:, 0] + pdX[:, 1] if pdX is not None else None, pdh0.sum(dim=1) if pdh0 is not None else None, pA.sum(dim=0), pB.sum(dim=0),
+                pb.sum(dim=0) if bias2 is not None else None, pwf.sum(dim=0), pbf.sum(dim=0) if ctx.has_bf else None, None)
+
+
+def small_node_gates(X, h0, wA2, wB2, bias2, wf2, bf2, graph):
+    """Node gates [2][B][T][N] (input, forget) of a small-graph cell; shapes: small_node_gates_supported."""
+    require_device(X, h0, wA2, wB2, wf2)
+    return _SmallNodeGates.apply(X, h0, wA2, wB2, bias2, wf2, bf2, graph)
+
+
 # ------------------------------------------------------------------------------------------ small-graph edge-gated cell
 def small_edge_supported(N, nnz, nnz_support, G, F, Kin, Kst, dtype, E=1):
     if E != 1 or dtype not in (torch.float32, torch.float64):

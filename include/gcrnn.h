@@ -888,6 +888,37 @@ int gcrnn_small_gates_backward_dx(int dtype, const void* X, const void* h0, cons
                                   void* plb, void* pdh0, void* pdX, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
                                   int64_t Kin, int64_t Kst, void* stream);
 
+/* Node gates of the small-graph regime (GGCRNNCell node gating, graphML.py:2379-2399), both gates in one launch: the time gates' gate
+ * cell read out by an F -> 1 graph filter in place of the Linear,
+ *   d_t = tanh(A_g(S) x_t + B_g(S) h0 + 2 b_g)   [F][N],     g = 0 input, 1 forget   (h0, never h_{t-1})
+ *   gate[g][b][t][n] = sigmoid( bf_g + sum_{k < Kst} sum_f wf_g[k][f] (d_t S^k)[f][n] ).
+ * Parameters stacked over the two gates: wA2 [2][F][Kin][G], wB2 [2][F][Kst][F], bias2 [2][F] or NULL, wf2 [2][Kst][F]
+ * (GraphFilter.weight[0, 0] of the two F -> 1 filters), bf2 [2] or NULL; Sdense [N][N] as gcrnn_small_dense_forward. gate [2][B][T][N]:
+ * gate[g] is the [B][T][N] tensor gcrnn_small_dense_* reads with strides (T N, N, 1). The filter is evaluated taps first,
+ * u_k = wf[k] . d_t, then Horner u_k += u_{k+1} S for k = Kst - 2 .. 0, each sum in a fixed order and without atomics: two runs give
+ * the same bits. backward: dl [2][B][T][N] = d loss / d (pre-sigmoid value) -- the caller forms dgate . gate . (1 - gate), as for the
+ * time gates' dsum; per-sequence partial sums (added by the caller in a fixed order) pA [B][2][F][Kin][G], pB [B][2][F][Kst][F],
+ * pb [B][2][F], pwf [B][2][Kst][F], pbf [B][2], pdh0 [B][2][F][N] (or NULL); every element of every output is written.
+ * gcrnn_small_node_gates_backward_dx: the same pass with each gate's share of the input gradient as well, pdX [B][2][T][G][N]
+ * (required). gcrnn_small_node_gates_supported: fp32 / fp64, gcrnn_small_gates_supported(dtype, N, G, F, Kin, Kst, backward),
+ * gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated = 1), and the LDS image fits in 160 KB: the time gates'
+ * image plus Kst F values (backward: 2 Kst F) and, only where Kst > F rounded up to 4, Kst rows of N more; backward = 1 answers for
+ * both backward entry points. Answers without a device.
+ * Checked before any launch, in this order: GCRNN_ERR_NULL_POINTER, GCRNN_ERR_BAD_DTYPE, GCRNN_ERR_BAD_SHAPE (B, T or a dimension
+ * <= 0), GCRNN_ERR_UNSUPPORTED where the query says no. */
+int gcrnn_small_node_gates_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int backward);
+int gcrnn_small_node_gates_forward(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2,
+                                   const void* wf2, const void* bf2, const void* Sdense, void* gate, int64_t B, int64_t T,
+                                   int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, void* stream);
+int gcrnn_small_node_gates_backward(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2, const void* bias2,
+                                    const void* wf2, const void* Sdense, const void* dl, void* pA, void* pB, void* pb, void* pwf,
+                                    void* pbf, void* pdh0, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin,
+                                    int64_t Kst, void* stream);
+int gcrnn_small_node_gates_backward_dx(int dtype, const void* X, const void* h0, const void* wA2, const void* wB2,
+                                       const void* bias2, const void* wf2, const void* Sdense, const void* dl, void* pA, void* pB,
+                                       void* pb, void* pwf, void* pbf, void* pdh0, void* pdX, int64_t B, int64_t T, int64_t N,
+                                       int64_t G, int64_t F, int64_t Kin, int64_t Kst, void* stream);
+
 /* EDGE-gated cell of the small-graph regime (spatial_gating = 'edge', graphML.py:2411-2416 with graphAttention, graphML.py:521-627;
  * one head, one edge feature, concatenated, ReLU), inference: h_t = tanh(gi_t att_in(A(S) x_t + b) + gf_t att_f(B(S) h_{t-1} + b)).
  * Two launches whatever T is: the input branch of every (b, t) at once into the scratch Ya [B][T][F][N], then the recurrence with
