@@ -97,6 +97,7 @@ def _bind(lib):
         'gcrnn_fused_forward_wide_head_bf16': (C.c_int, [_c_p] * 3 + [_c_i64] + [_c_p] * 7 + [_c_i64] * 7 + [_c_p] * 7),
         'gcrnn_fused_pack_weights_wide_bias': (C.c_int, [C.c_int] + [_c_p] * 5 + [_c_i64] * 5 + [C.c_double, _c_p]),
         'gcrnn_fused_forward_wide_user_bytes': (_c_i64, [_c_i64] * 3),
+        'gcrnn_fused_forward_wide_resident_tiles': (C.c_int, [_c_i64] * 4 + [C.c_int]),
         'gcrnn_fused_forward_wide_user_supported': (C.c_int, [_c_i64] * 7 + [C.c_double, C.c_int]),
         'gcrnn_fused_forward_wide_user_bf16': (C.c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64] + [_c_p] * 5 + [_c_i64] * 7 + [_c_p, C.c_int, _c_p, _c_p, _c_p, _c_p]),
         'gcrnn_fused_forward_wide_head_user_supported': (C.c_int, [_c_i64] * 7 + [C.c_double, C.c_int]),

@@ -185,19 +185,34 @@ __device__ __forceinline__ int lane_now() {
     }                                                                                              \
   } while (0)
 
-template <int K, int HS, int XS>
+// RT > 0 (resident tiles; the un-gated self-start forward with more than one chunk): the weight fragments live in a RING of three taps
+// instead of a whole chunk's K -- a hop reads ONE tap, and the taps are consumed in a fixed order (chunk 0: tap K-1 .. 0, chunk 1: tap
+// K-1 .. 0, the next step ...), so item g of that order sits in slot g % 3 and arrives by LDS-DMA two hops before it is read. Behind the
+// ring, in the bytes it frees, lies a block of RT tiles per wave and re-read chunk: [HS-1][SWAVES][RT] x 1 KB, lane-linear (16 bytes per
+// lane), where a wave keeps the state fragments of its first RT tiles between the epilogue that makes them and the next step's operand
+// instead of sending them through the state scratch. At K = 5, F = G = 64: 24 KB ring + 16 KB block = the 40 KB of today's WB.
+template <int K, int HS, int XS, int RT = 0>
 struct Seq32Map {
   static constexpr int KS = HS + XS;
   static constexpr int PL = GCRNN_HOP_WIDE_PLANE;          // plane 1 of the hop image
   static constexpr int RS2 = 4 * NP + 16;                  // row of the transposed user-layout tile: [feature pair][node] words; q and q + 1 sit 16 banks apart
   static constexpr int BIAS_OFF = PL + 32 * 1024;          // behind plane 1 (the transposed tile, 16 rows, ends below it)
   static constexpr int FLAG_OFF = BIAS_OFF + 256;
-  static constexpr int WOFF = 2 * PL;                      // one chunk's weight fragments
-  static constexpr int WB = K * KS * 2048;
-  static constexpr int COL_OFF = WOFF + WB;
+  static constexpr int WOFF = 2 * PL;                      // the weight fragments: one chunk's, or the ring
+  static constexpr int RING = RT > 0 ? 3 : K;              // taps held in LDS
+  static constexpr int TAPB = KS * 2048;                   // one tap's fragments: 2 KS pieces of 1 KB
+  static constexpr int WCH = K * TAPB;                     // one chunk's fragments in the packed weights (global memory)
+  static constexpr int WB = RING * TAPB;
+  static constexpr int RES_OFF = WOFF + WB;                // resident tiles: wave-private, lane-linear
+  static constexpr int RES_B = RT * (HS - 1) * SWAVES * 1024;
+  static constexpr int COL_OFF = RES_OFF + RES_B;
   static constexpr int NPCK = 128;                         // nodes per inline-pack round
   static constexpr int PFS = 256;                          // prefetch scratch (one dword per lane)
   static_assert(16 * RS2 <= BIAS_OFF && FLAG_OFF + 768 <= WOFF, "LDS map");
+  static_assert(RT >= 0 && RT <= STILES && (RT == 0 || HS > 1), "resident tiles: a share of a wave's tiles, of a state with a re-read chunk");
+  // planes / transposed tile, bias and flag tables < WOFF <= ring < RES_OFF <= block < COL_OFF <= column words, slot table, (rank-1
+  // factors, head table,) pack tile, PFS: lds_bytes() lays those out upwards from COL_OFF, so nothing overlaps the block
+  static_assert(WOFF + RING * TAPB == RES_OFF && RES_OFF + RES_B == COL_OFF && RES_OFF % 1024 == 0, "LDS map: ring, resident block, column words");
   static size_t lds_bytes(int64_t entries, bool inline_pack, bool r1 = false) {
     const size_t need = (size_t)COL_OFF + (size_t)entries * 32 + GCRNN_HOP_COLUMN_PAD + NP * 4 + (r1 ? 2 * NP * 4 : 0) + (inline_pack ? (size_t)(32 * (XS > 0 ? XS : HS)) * NPCK * 2 : 0)
                         + PFS;      // (the last PFS bytes: where gcrnn_fused_seq32p.h's L2 prefetches land -- LDS-DMA needs a destination, nobody reads it)
@@ -246,7 +261,11 @@ struct Seq32Map {
 // SPLIT: batches that leave half of the chip idle (65 <= B <= 128 at F = 64): a sequence's F/32 chunks run as F/32 WORKGROUPS, one launch per time
 //     step (the launch boundary is the hand-over between them: no cross-workgroup wait inside a launch). Each loads the whole operand, runs its
 //     chunk, stores its 32 features and lays out its share of the next step's input; nothing is kept in registers across steps.
-template <int K, int HS, int XS, int VAR, int MODE = 0, bool GATED = false, bool R1 = false, bool SPLIT = false>
+// RT (Seq32Map; VAR 7 only, HS > 1): the tap ring, and the first RT tiles of every wave hand their chunks 0 .. HS-2 to the next step through
+//     the wave-private LDS block instead of the state scratch. The block is written in step t and read in step t + 1 of the SAME workgroup
+//     and sequence only (step 0 reads h0), so nothing carries over to a workgroup that runs on the CU afterwards, or to the next sequence of
+//     a persistent workgroup. RT = 0: one chunk's K taps in LDS and every tile through the scratch, the kernel as it was.
+template <int K, int HS, int XS, int VAR, int MODE = 0, bool GATED = false, bool R1 = false, bool SPLIT = false, int RT = 0>
 __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a) {
   static_assert(!R1 || !SPLIT, "rank-1 graphs: every mode of the persistent form (the BPTT chain takes the adjoint plan: the factors swap)");
   static_assert(!SPLIT || ((MODE == 0 || MODE == 2) && !R1 && HS > 1), "split sequences: the (un-gated or time-gated) forward and the BPTT chain, with more than one chunk");
@@ -262,11 +281,13 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   constexpr int SCR_CH = NP * 64;            // bytes of one chunk's scratch rows [NP slots][32] bf16
   static_assert(MODE == 0 || ((MODE >= 1 && MODE <= 4) && !GATED), "modes");
   static_assert(MODE < 3 || (!R1 && !SPLIT), "modes 3, 4: uniform-weight graphs, persistent form");
-  using M = Seq32Map<K, HS, XS>;
+  using M = Seq32Map<K, HS, XS, RT>;
+  constexpr bool RINGV = RT > 0;
+  static_assert(!RINGV || (VAR == 7 && MODE == 0 && !GATED && !SPLIT && HS > 1), "resident tiles: the un-gated self-start forward, more than one chunk");
   constexpr int KS = HS + XS;
   constexpr int F = 32 * HS, G = 32 * XS;
   constexpr int NCH = (MODE == 1) ? 2 * HS : HS;  // 32-feature output chunks
-  constexpr int PL = M::PL, WOFF = M::WOFF, WB = M::WB, COL_OFF = M::COL_OFF, RS2 = M::RS2;
+  constexpr int PL = M::PL, WOFF = M::WOFF, WCH = M::WCH, TAPB = M::TAPB, COL_OFF = M::COL_OFF, RS2 = M::RS2;
   constexpr int NPCK = M::NPCK, NRND = NP / NPCK, NH = NCH * (K - 1), RPH = (NRND + NH - 1) / NH;      // pack rounds per step / hops per step / rounds per hop
   constexpr int PKROWS = SONLY ? F : G;
   static_assert(STILES == 8 && GCRNN_HOP_ASM && K >= 2 && (SONLY ? XS == 0 : XS > 0), "generated hop stream: 8 tiles per wave; the chain's operand is the state alone");
@@ -444,6 +465,16 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
     }
   };
 
+  // RT > 0: the ring at the top of a sequence -- items 0 and 1 of the order (chunk 0's taps K-1 and K-2) in slots 0 and 1; hop 1 brings items 2, 3
+  [[maybe_unused]] auto ring_start = [&]() {
+    const char* w0 = reinterpret_cast<const char*>(a.wpack);
+    const int ln = lane_now();
+    for (int p = wave; p < 2 * (TAPB / 1024); p += SWAVES) {
+      const int item = p / (TAPB / 1024), piece = p - item * (TAPB / 1024);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w0 + (K - 1 - item) * TAPB + piece * 1024 + ln * 16),
+                                       (__attribute__((address_space(3))) void*)(smem + WOFF + p * 1024), 16, 0, 0);
+    }
+  };
   {
     const int cbytes = entries * 32;
     const char* csrc = reinterpret_cast<const char*>(a.ell_col4);
@@ -451,8 +482,10 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       if (p * 1024 + lane * 16 < cbytes)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(csrc + p * 1024 + lane * 16),
                                          (__attribute__((address_space(3))) void*)(smem + COL_OFF + p * 1024), 16, 0, 0);
-    const char* wsrc = reinterpret_cast<const char*>(a.wpack) + (size_t)chunk0 * WB;      // (SPLIT: this workgroup's chunk)
-    for (int p = wave; p < WB / 1024; p += SWAVES)
+    const char* wsrc = reinterpret_cast<const char*>(a.wpack) + (size_t)chunk0 * WCH;      // (SPLIT: this workgroup's chunk)
+    if constexpr (RINGV) ring_start();
+    else
+    for (int p = wave; p < WCH / 1024; p += SWAVES)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + p * 1024 + lane * 16),
                                        (__attribute__((address_space(3))) void*)(smem + WOFF + p * 1024), 16, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -514,6 +547,15 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
   };
   bool have_operand = self_start;      // (wave-uniform; self-start: the one sequence's operand is in the registers already)
   for (int b = wg_seq; b < B; b += gseq) {
+  if constexpr (RINGV) {
+    // a persistent workgroup's next sequence: the order starts over (the last step's hops brought items of a step that never ran; every
+    // wave is behind the last epilogue's end barrier, so nobody reads the ring)
+    if (b != wg_seq) {
+      ring_start();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      lds_barrier();
+    }
+  }
   if (!have_operand) load_first_operand(b);
   have_operand = false;
 #pragma unroll 1
@@ -563,12 +605,17 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 
     f32x4 acc[STILES][2];
     // acc[i][h] += W_tap(c, half h) [h|x]^T for the wave's 8 tiles: one weight fragment feeds 8 independent MFMA chains
-    auto taps = [&](int tap, [[maybe_unused]] bool on_sums = false) {
+    // (ch: the chunk the tap belongs to -- RT > 0: item (step NCH + ch) K + (K-1 - tap) of the order, in slot item % 3)
+    auto tap_off = [&](int ch, int tap) -> uint32_t {
+      if constexpr (RINGV) return ((uint32_t)((step * NCH + ch) * K + (K - 1 - tap)) % 3u) * (uint32_t)TAPB;
+      else return (uint32_t)(tap * TAPB);
+    };
+    auto taps = [&](int ch, int tap, [[maybe_unused]] bool on_sums = false) {
 #ifdef GCRNN_SEQ32_EXPERIMENT_NO_HOP_TAPS      // timing experiment, WRONG results: what would a hop cost if its tap were free (hidden inside the stream)?
       if (tap != K - 1) return;
 #endif
       const int ln = lane_now();                       // (the fragment address is re-derived per call, not kept -- or spilled -- across the hops)
-      const uint32_t wofs = (uint32_t)WOFF + (uint32_t)ln * 16u;
+      const uint32_t wofs = (uint32_t)WOFF + (uint32_t)ln * 16u + tap_off(ch, tap);
       if constexpr (GATED) {
         // gi (x W_x) + gf (h W_h) on ONE accumulator chain per half: h-chain, scale by gf / gi, continue with x, scale by gi (gi = sigmoid(.) > 0;
         // the wave-uniform guard covers an underflowed gate). Waves 4..7 (tap first): the accumulators are ZERO on entry and the stream then
@@ -587,7 +634,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           if (hpart) {
 #pragma unroll
             for (int s = 0; s < HS; ++s) {
-              const bf16x8 afr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)(((tap * 2 + h) * KS + s) * 1024)));
+              const bf16x8 afr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)((h * KS + s) * 1024)));
 #pragma unroll
               for (int i = 0; i < STILES; ++i) acc[i][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr[i][s], acc[i][h], 0, 0, 0);
             }
@@ -599,7 +646,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           if (xpart) {
 #pragma unroll
             for (int s = HS; s < KS; ++s) {
-              const bf16x8 afr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)(((tap * 2 + h) * KS + s) * 1024)));
+              const bf16x8 afr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)((h * KS + s) * 1024)));
 #pragma unroll
               for (int i = 0; i < STILES; ++i) acc[i][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr[i][s], acc[i][h], 0, 0, 0);
             }
@@ -616,18 +663,18 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 #pragma unroll
           for (int s = 0; s < KS; ++s) {
             if (s < HS && skip_h) continue;
-            const bf16x8 afr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)(((tap * 2 + h) * KS + s) * 1024)));
+            const bf16x8 afr = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)((h * KS + s) * 1024)));
 #pragma unroll
             for (int i = 0; i < STILES; ++i) acc[i][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr[i][s], acc[i][h], 0, 0, 0);
           }
       } else {
       // (the next fragment is requested before the current one's eight MFMAs)
       uint4 af[2];
-      af[0] = *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)((tap * 2 * KS) * 1024));
+      af[0] = *reinterpret_cast<const uint4*>(smem + wofs);
 #pragma unroll
       for (int hs = 0; hs < 2 * KS; ++hs) {
         const int h = hs / KS, s = hs - h * KS;
-        if (hs + 1 < 2 * KS) af[(hs + 1) & 1] = *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)((tap * 2 * KS + hs + 1) * 1024));
+        if (hs + 1 < 2 * KS) af[(hs + 1) & 1] = *reinterpret_cast<const uint4*>(smem + wofs + (uint32_t)((hs + 1) * 1024));
         const bf16x8 afr = __builtin_bit_cast(bf16x8, af[hs & 1]);
 #pragma unroll
         for (int i = 0; i < STILES; ++i) acc[i][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr[i][s], acc[i][h], 0, 0, 0);
@@ -655,20 +702,20 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       }
     };
     // seed of a chunk: tap K-1 goes straight into the hop image (every wave has left the image: the barrier before)
-    auto seed = [&]() {
+    auto seed = [&](int ch) {
 #pragma unroll
       for (int i = 0; i < STILES; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-      taps(K - 1);
+      taps(ch, K - 1);
       put(std::false_type{});
     };
     // The seed's tap alone, for the chunk boundaries where it runs beside the user-layout row stores: it reads the operand and the weight
     // fragments only, so the image's place may still hold the transposed tile.
-    auto seed_taps_beside_rows = [&]() {
+    auto seed_taps_beside_rows = [&](int ch) {
 #pragma unroll
       for (int i = 0; i < STILES; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-      taps(K - 1);
+      taps(ch, K - 1);
     };
-    seed();
+    seed(chunk0);
 
 #pragma unroll 1
     for (int chunk = chunk0; chunk < (SPLIT ? chunk0 + 1 : NCH); ++chunk) {
@@ -782,16 +829,26 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       // vmcnt(0) + barrier, and no LDS-DMA is pending during an epilogue -- hipcc orders each LDS access of a wave behind its pending
       // LDS-DMA pieces with a vmcnt(0), which in the last epilogue would also wait for the next operand's requests.
       auto r0_of = [&](int j) { return (chunk * (K - 1) + (j - 1)) * RPH; };
-      auto weights_issue = [&](int wc, int tap) {
-        const char* wsrc = reinterpret_cast<const char*>(a.wpack) + (size_t)wc * WB + (size_t)tap * (2 * KS * 1024);
+      // RT > 0 (the ring): hop j reads item j of its chunk (the seed item 0) and brings item j + 2 -- hop 1 also item 2 -- into the slots of
+      // items j - 1 (read in hop j - 1, or by the seed in front of the chunk's first barrier) and -1 (the previous chunk's tap 0, read in its
+      // last hop): K items in K - 1 hops as before, in front of the stream as before, each covered by its hop's wait, two hops ahead of its
+      // reader instead of a chunk ahead. Items K and K + 1 are the next chunk's taps K-1 and K-2: both have landed when the seed taps run
+      // beside the row stores, and no LDS-DMA is pending in an epilogue -- at K = 2 either, which needs no wait at the chunk's end any more.
+      auto weights_issue = [&](int wc, int tap, uint32_t dst = 0xffffffffu) {
+        if (dst == 0xffffffffu) dst = (uint32_t)(tap * TAPB);
+        const char* wsrc = reinterpret_cast<const char*>(a.wpack) + (size_t)wc * WCH + (size_t)tap * (2 * KS * 1024);
         const int lane = lane_now();
 #pragma unroll
         for (int i = 0; i < (2 * KS + SWAVES - 1) / SWAVES; ++i) {
           const int piece = i * SWAVES + wave;
           if (piece < 2 * KS)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + piece * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(smem + WOFF + tap * (2 * KS * 1024) + piece * 1024), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void*)(smem + WOFF + dst + piece * 1024), 16, 0, 0);
         }
+      };
+      [[maybe_unused]] auto ring_issue = [&](int pos) {      // item `pos` of this chunk's order, K <= pos: the next chunk's
+        const int nx = pos >= K ? 1 : 0;
+        weights_issue(nx ? (chunk + 1) % NCH : chunk, K - 1 - (pos - nx * K), ((uint32_t)((step * NCH + chunk) * K + pos) % 3u) * (uint32_t)TAPB);
       };
       // MODE 2: the epilogue's operands h_{t-1}, dH_{t-1} of this lane's (node, 8 features) per tile. Requested in the write-back phases of hops
       // 1 .. EPH (behind the hop's vmcnt(0) + barrier), a share of the tiles each: they land under the NEXT hop's stream and are covered by its
@@ -849,6 +906,10 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       auto hop = [&](auto jc) __attribute__((always_inline)) {
         constexpr int j = decltype(jc)::value;
         auto dma_issue = [&]() {      // this wave's LDS-DMA pieces of the hop, right in front of its stream
+          if constexpr (RINGV) {
+            if (j == 1) ring_issue(2);
+            ring_issue(j + 2);
+          } else
           if (NCH > 1 && !SPLIT) {
             weights_issue((chunk + 1) % NCH, K - j);
             if (j == 1 && K > 2) weights_issue(chunk, 0);
@@ -876,9 +937,9 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           r1_scale(acc, 0);      // R1: sums of a (.) v over the in-neighbours, times b[n]: then the tap
           GCRNN_STAMP32(1 + chunk * 24 + 4 * (j - 1) + 1);
           if (j == 2 && chunk == 0) GCRNN_STAMP32_WAVE(56);
-          taps(K - 1 - j, true);
+          taps(chunk, K - 1 - j, true);
         } else {
-          taps(K - 1 - j);
+          taps(chunk, K - 1 - j);
           r1_scale(acc, 1);      // R1: the tap in units of b (t' = t / b)
           if (j == 2 && chunk == 0) GCRNN_STAMP32_WAVE(56);
           dma_issue();
@@ -906,7 +967,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         if constexpr (R1 && j == K - 1) {
           if (!stream_first) r1_scale(acc, 2);      // the chunk's result: t_0 = b (.) t'_0
         }
-        if (K == 2 && NCH > 1 && !SPLIT) weights_issue((chunk + 1) % NCH, 0);      // (K = 2: tap 0's fragments are free only now, and needed at the next chunk's only hop)
+        if (K == 2 && NCH > 1 && !SPLIT && !RINGV) weights_issue((chunk + 1) % NCH, 0);      // (K = 2: tap 0's fragments are free only now, and needed at the next chunk's only hop)
         if (r0 < NRND) pack_drain(r0);
 #pragma unroll
         for (int e = 1; e < RPH; ++e) {       // (fewer hops than rounds: the extra rounds are not hidden behind a stream)
@@ -952,7 +1013,9 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
 #ifdef GCRNN_SEQ32_EXPERIMENT_SKIP      // timing experiment, WRONG results: 1 = no state requests, 2 = no input requests (which half of the operand costs the wait?)
             if ((GCRNN_SEQ32_EXPERIMENT_SKIP == 1) == (s < HS)) continue;
 #endif
-            if (SCRV && s < HS)      // this lane's own 16 bytes of the scratch (slot order: no slot word), sc1
+            if (RINGV && s < HS && i < RT)      // resident tile: this lane's own 16 bytes of the wave's block (no barrier: the wave wrote them itself, in chunk s's epilogue)
+              bfr[i][s] = *reinterpret_cast<const bf16x8*>(smem + M::RES_OFF + ((s * SWAVES + wave) * RT + i) * 1024 + lane_now() * 16);
+            else if (SCRV && s < HS)      // this lane's own 16 bytes of the scratch (slot order: no slot word), sc1
               bfr[i][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_sn, (lane_now() & 15) * 64 + 16 * qo, s * SCR_CH + (wave * STILES + i) * 1024, 16));
             else if (s < HS)
               bfr[i][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_hn, (w >> 16) * (F * 2) + 16 * qo + 64 * s, b * (NP * F * 2), GCRNN_SEQ32_NT_XLOAD));
@@ -1182,7 +1245,11 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         if constexpr (SCRV) {
           // chunks 0 .. HS-2 into the workgroup's scratch at the lane's SLOT (padding slots store their zeros every step: the next step reads
           // them back); the last chunk's features stay in registers and leave through the user-layout tile only
-          if (!last) __builtin_amdgcn_raw_buffer_store_b128(p, scratch_rsrc(), (lane & 15) * 64 + 16 * q, chunk * SCR_CH + (wave * STILES + i) * 1024, 0);
+          // (RT > 0: the wave's first RT tiles stay on chip -- one 16-byte LDS store, lane-linear, read back by request_next_operand)
+          if (!last) {
+            if (RINGV && i < RT) *reinterpret_cast<u32x4_t*>(smem + M::RES_OFF + ((chunk * SWAVES + wave) * RT + i) * 1024 + lane * 16) = p;
+            else __builtin_amdgcn_raw_buffer_store_b128(p, scratch_rsrc(), (lane & 15) * 64 + 16 * q, chunk * SCR_CH + (wave * STILES + i) * 1024, 0);
+          }
         } else
         if (GCRNN_SEQ32_NT_STATE && last) __builtin_amdgcn_raw_buffer_store_b128(p, rsrc_o, node * (F * 2) + (chunk * 32 + q * 8) * 2, b * (NP * F * 2), GCRNN_SEQ32_NT_STATE);
         else __builtin_amdgcn_raw_buffer_store_b128(p, rsrc_o, node * (F * 2) + (chunk * 32 + q * 8) * 2, b * (NP * F * 2), 0);
@@ -1210,6 +1277,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
         for (int i = 0; i < STILES; ++i) bfr[i][HS - 1] = __builtin_bit_cast(bf16x8, pkd[i]);
       }
       if (GCRNN_SEQ32_OPERAND_AT == 1) request_next_operand();
+      GCRNN_STAMP32(1 + chunk * 24 + 22);      // (diagnostic builds: the next operand's requests and the resident reload are issued)
       if constexpr (ITEMS) {
         // the workgroup's next item: its input was laid out by this item's pack rounds (stored, waited for and behind barriers since the
         // first half of the hops) or by the caller; its state operand is h0
@@ -1247,7 +1315,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       constexpr bool OVL = USERV && MODE == 0 && !GATED && !SPLIT;
       const bool ovl = OVL && chunk + 1 < NCH;
       if (ovl && wave < SWAVES / 2) {
-        seed_taps_beside_rows();
+        seed_taps_beside_rows(chunk + 1);
         GCRNN_STAMP32(1 + chunk * 24 + 21);
       }
       if (aux1) {
@@ -1288,7 +1356,7 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
           }
         }
       }
-      if (ovl && wave >= SWAVES / 2) seed_taps_beside_rows();
+      if (ovl && wave >= SWAVES / 2) seed_taps_beside_rows(chunk + 1);
       // this chunk's stores have retired (the next step reads some of them back; K = 2: the next chunk's tap 0 has landed), the tile
       // has been read: the image may be seeded again
       if (GCRNN_SEQ32_OPERAND_AT == 2) request_next_operand();
@@ -1297,13 +1365,13 @@ __global__ __launch_bounds__(STHREADS) void fused_seq32_kernel(const Seq32Args a
       // its hop's wait, the stores the next step reads back (the earlier chunks' states, the pack's rows) have been behind a hop's vmcnt(0)
       // since, and the next operand's requests are waited for where the seed's MFMAs first use them (hipcc counts them: the state fragments
       // were requested first, so the seed starts on them while the input's are still landing).
-      if (K == 2 && NCH > 1 && !SPLIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (K == 2 && NCH > 1 && !SPLIT && !RINGV) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else if (GCRNN_SEQ32_END_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       lds_barrier();
       GCRNN_STAMP32(1 + chunk * 24 + 20);
       if (!SPLIT && chunk + 1 < NCH) {
         if (ovl) put(std::false_type{});      // (its taps ran beside the row stores)
-        else seed();
+        else seed(chunk + 1);
       }
     }  // chunks
   }  // steps

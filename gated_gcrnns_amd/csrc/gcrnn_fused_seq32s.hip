@@ -19,9 +19,18 @@ static int seq32s_launch_v(const Seq32Args& sa, size_t lds, hipStream_t st) {
   return GCRNN_OK;
 }
 
+// the VAR 7 forward on resident tiles (gcrnn_fused_seq32r.hip): its LDS bytes -- 0 when it does not take the launch -- and its launcher
+size_t gcrnn_seq32r_lds(int K, int HS, int XS, int64_t entries, bool r1, int* rt);
+int gcrnn_seq32r_forward(const Seq32Args& sa, int K, int XS, int rt, size_t lds, hipStream_t st);
+
 template <int K, int HS, int XS>
 static int seq32s_launch(const Seq32Args& sa, bool inline_pack, size_t lds, hipStream_t st) {
   if (!sa.a1 || (HS > 1 && !sa.scr)) return GCRNN_ERR_NULL_POINTER;
+  if (HS > 1 && inline_pack && !sa.gi0) {      // un-gated, as the module issues it: resident tiles where the map has room for them
+    int rt = 0;
+    const size_t ldsr = gcrnn_seq32r_lds(K, HS, XS, sa.entries, sa.r1a != nullptr, &rt);
+    if (ldsr) return gcrnn_seq32r_forward(sa, K, XS, rt, ldsr, st);
+  }
   if (sa.gi0) {      // time-gated recurrence: the gate pre-pass has laid out X
     if (inline_pack) return GCRNN_ERR_BAD_SHAPE;
     return sa.r1a ? seq32s_launch_v<K, HS, XS, 6, true, true>(sa, lds, st) : seq32s_launch_v<K, HS, XS, 6, true, false>(sa, lds, st);

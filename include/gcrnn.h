@@ -502,8 +502,14 @@ int gcrnn_fused_forward_wide_head_bf16(const void* xs, const void* h0, void* scr
  *   its `xs` the work buffer, with no size to check it against -- for callers that are bound to that symbol (the Python dispatch is: its
  *   launch-count tests pin it). Every other non-zero value keeps meaning "last state only", as before.
  * gcrnn_fused_pack_weights_wide_bias: gcrnn_fused_pack_weights_wide that also writes bias_out [Fout] fp32 = the cell's bias [Fout] (dtype of
- *   the taps) in the same launch -- the `bias` argument of the wide forwards, without a conversion launch of its own. */
+ *   the taps) in the same launch -- the `bias` argument of the wide forwards, without a conversion launch of its own.
+ * gcrnn_fused_forward_wide_resident_tiles: the tiles per wave (0, 2 or 3) whose re-read state chunk the un-gated inline-pack forward on the state
+ *   scratch (the launch behind gcrnn_fused_forward_wide_user_bf16, and behind _scratch_bf16 with Xuser_inline) keeps in LDS instead of the
+ *   scratch, with the tap weights in a ring of three taps (gcrnn_fused_seq32.h, RT). 0: F != 64, no LDS room beside this graph's column
+ *   words, or GCRNN_SEQ32_RESIDENT=0 in the environment (read at every call: the launch as it was, same binary; =2: at most two tiles).
+ *   H is bit-identical either way. */
 #define GCRNN_WIDE_SELF_START 2
+int gcrnn_fused_forward_wide_resident_tiles(int64_t F, int64_t G, int64_t K, int64_t entries, int rank1);
 int gcrnn_fused_pack_weights_wide_bias(int wdtype, const void* wA, const void* wB, const void* bias, void* wpack, float* bias_out, int64_t Fout,
                                        int64_t F, int64_t G, int64_t Kin, int64_t Kst, double uniform_w, void* stream);
 int64_t gcrnn_fused_forward_wide_user_bytes(int64_t B, int64_t T, int64_t G);

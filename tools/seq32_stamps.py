@@ -69,7 +69,9 @@ dll = ctypes.CDLL(lib)
 p32 = os.environ.get('GCRNN_SEQ32P')
 pinned = not (chain or gates) and (p32 != '0' if native else (p32 is not None and p32 != '0'))
 scratch = not (chain or gates or native or pinned) and os.environ.get('GCRNN_SEQ32_STATE_SCRATCH', '1') != '0'
-reader = dll.gcrnn_debug_read_seq32p_stamps if pinned else dll.gcrnn_debug_read_seq32s_stamps if scratch else dll.gcrnn_debug_read_seq32_stamps
+# ... and within it the resident-tile launch (gcrnn_fused_seq32r.hip) where the library has one and GCRNN_SEQ32_RESIDENT does not switch it off
+resident = scratch and hasattr(dll, 'gcrnn_fused_forward_wide_resident_tiles') and os.environ.get('GCRNN_SEQ32_RESIDENT', '1')[:1] != '0'
+reader = dll.gcrnn_debug_read_seq32p_stamps if pinned else dll.gcrnn_debug_read_seq32r_stamps if resident else dll.gcrnn_debug_read_seq32s_stamps if scratch else dll.gcrnn_debug_read_seq32_stamps
 assert reader(buf.ctypes.data_as(ctypes.c_void_p)) == 0
 st = buf.reshape(256, 96).astype(np.int64)
 names = {0: 'step start (operand in registers)'}
@@ -82,13 +84,16 @@ for c in range(4 if gates else 2):
         names[b0 + 4 * (j - 1) + 3] = 'c%d hop %d dma wait + barrier' % (c, j)
         names[b0 + 4 * (j - 1) + 4] = 'c%d hop %d put + weights dma + pack drain + barrier' % (c, j)
     names[b0 + 17] = 'c%d next operand requests + tanh + state stores' % c
+    if (st[:, b0 + 22] > st[:, b0 + 17]).all():      # (libraries with the stamp behind the requests: the boundary reads as requests + reload / tile / rows)
+        names[b0 + 17] = 'c%d tanh + state stores' % c
+        names[b0 + 22] = 'c%d next operand requests + resident reload issued' % c
     names[b0 + 18] = 'c%d transposed tile + barrier' % c
     if (st[:, b0 + 21] > st[:, b0 + 18]).all():      # (the next chunk's seed taps beside the row stores: wave 0 evaluates them first)
         names[b0 + 21] = 'c%d next seed taps (wave 0; waves 4-7: rows)' % c
     names[b0 + 19] = 'c%d user-layout row stores' % c
     names[b0 + 20] = 'c%d vmcnt(0) + end barrier' % c
 prev = 0
-print('kernel unit: %s' % ('gcrnn_fused_seq32p' if pinned else 'gcrnn_fused_seq32s (state scratch, as issued)' if scratch else 'gcrnn_fused_seq32'))
+print('kernel unit: %s' % ('gcrnn_fused_seq32p' if pinned else 'gcrnn_fused_seq32r (state scratch + resident tiles, as issued)' if resident else 'gcrnn_fused_seq32s (state scratch, as issued)' if scratch else 'gcrnn_fused_seq32'))
 print('stamps of step T-3 of the persistent launch (%s), median over 256 workgroups; unit = 100 shader cycles (s_memtime)' % ('time gates, pair pre-pass: first item of a workgroup, X laid out by the caller' if gates else 'BPTT data chain, inline layout of dH' if chain else 'native layout' if native else 'user layout + inline pack'))
 tot = {}
 for s in names:      # (insertion order = order in time)
