@@ -268,6 +268,20 @@ class GatedGCRNNforClassification(_GatedGCRNNBase):
                 for layer in self.outputNN[1:]:                      # finalNonlinearity, where there is one
                     y = layer(y)
                 return y
+        if self.gnn_head:
+            sel = self.outputNN[0]
+            if sel.L == 1 and list(sel.F) == [self.F_h, 1] and len(sel.dimLayersMLP) == 1 and len(sel.MLP) == 1 and \
+                    type(sel.GFL[1]) in _FUSED_ACTIVATIONS and sel.GFL[0].weight.dtype == x.dtype:
+                # a head of ONE graph-filter layer with one output feature and one Linear behind a fused activation, on a small graph: the
+                # last state's hop levels, the filter, the activation and the read-out run in the forward launch, the BPTT launch starts
+                # from dlogits -- neither the T states (inference) nor dH (training) are materialised; None: not that path. The
+                # parameters are read at every call
+                gfl, lin = sel.GFL[0], sel.MLP[0]
+                y = self.stateGCRNN.classify_gnn(x, h0, gfl.weight, gfl.bias, _FUSED_ACTIVATIONS[type(sel.GFL[1])], lin.weight, lin.bias)
+                if y is not None:
+                    for layer in self.outputNN[1:]:                  # finalNonlinearity, where there is one
+                        y = layer(y)
+                    return y
         H = self.stateGCRNN(x, h0, last_only=not torch.is_grad_enabled())     # inference: only the last state is materialised
         h = H.select(1, -1)                                          # reference :1844
         if self.gnn_head:

@@ -937,6 +937,56 @@ class GGCRNNCell(nn.Module):
         return ops.small_cell_regress_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps,
                                           bias.view(1) if bias is not None else None, act, route[1], route[2])
 
+    @staticmethod
+    def _small_cls_gnn_head_pays(X, backward):
+        """Where the graph-filter head and read-out on the last state inside the matrix-core launches are no slower than the two-module
+        path (the acceptance rule of DESIGN 4.14, new median <= off median x (1 + off spread), on tools/small_cls_gnn_head_bench.py's rows,
+        DESIGN 4.16). backward: the training step (forward launch, BPTT launch seeded from dlogits) against the cell's two launches, the
+        zero-filled dH of `select` and graph_filter_layer's two; else inference with no state stored against the last-state launch +
+        graph_filter_layer + Linear. Measured at the epicenter driver's shape (adj59, F = 20, K = K_o = 4, C = 11, B = 100), this
+        path / the switched-off path in one process, median ms: all 36 rows pass. Inference at T = 20 / 200, un-gated: fp32 0.120 / 0.141
+        and 1.050 / 1.059, fp64 0.156 / 0.169 and 1.394 / 1.409; over the twelve rows at T >= 20 it gains 0.8 .. 17 %. The training step at
+        T = 20 / 200, un-gated: fp32 0.494 / 0.653 and 3.376 / 3.399, fp64 0.585 / 0.607 and 4.400 / 4.631; over the twelve rows at T >= 20
+        it gains 0.6 .. 32 %, the narrowest being fp64 time-gated T = 20, 1.1256 / 1.1323 inside an off spread of 0.5 %. T = 5 rows are
+        host time and bimodal (off spreads up to 51 %): reported, nothing claimed. So nothing is taken off the dispatch; a row that fails the
+        rule would be excluded here and named with its figures (GCRNN_SMALL_CLS_GNN_HEAD=all would still take it)."""
+        return True
+
+    def classify_gnn(self, X, h0, weight, bias, act, lin_weight, lin_bias):
+        """Cell + one graph-filter layer GraphFilter(F -> 1, K_o) + activation + Linear(N -> C) on the LAST state (the classification
+        model's Selection-GNN head with dimNodeSignals = [F, 1], nFilterTaps = [K_o], NoPool, dimLayersMLP = [C]; reference
+        architectures.py:1823-1849) inside the small-graph matrix-core launches (ops.small_cell_classify_gnn): un-gated, time-gated,
+        node-gated and time+node-gated cells, fp32 / fp64, E = 1. weight: the GraphFilter's F_out x E x K_o x F parameter with
+        F_out = E = 1, bias 1 x 1 or None, act a key of ops._GFL_ACTS, lin_weight C x N, lin_bias C or None. Inference: one launch for
+        recurrence and logits, no state is stored. Training: the forward launch stores the states BPTT reads, the head's output and the
+        logits; the BPTT launch starts from dlogits, so neither the zero-filled dH [B][T][F][N] of `H.select(1, -1)` nor an adjoint launch
+        exists. Returns logits B x C, or None when this cell / input / head does not run on that path (the model then continues on
+        forward() + SelectionGNN). GCRNN_NO_SMALL_CLS_GNN_HEAD=1 (read at every call) switches it off: A/B against the two-module path.
+        GCRNN_SMALL_CLS_GNN_HEAD=all takes every supported row, also those _small_cls_gnn_head_pays leaves to the two-module path."""
+        every = os.environ.get('GCRNN_SMALL_CLS_GNN_HEAD') == 'all'
+        if weight.dim() != 4 or weight.shape[0] != 1 or weight.shape[1] != 1 or self.E != 1 or act not in ops._GFL_ACTS:
+            return None
+        if bias is not None and bias.numel() != 1:
+            return None
+        if self.graph is None or lin_weight.dim() != 2 or lin_weight.shape[1] != self.N or lin_weight.dtype != X.dtype or \
+                (lin_bias is not None and lin_bias.dtype != X.dtype):
+            return None
+        C = lin_weight.shape[0]
+        # (a view, not weight[0, 0]: see regress_gnn)
+        taps = weight.reshape(weight.shape[2], weight.shape[3])
+        route = self._small_head_route(X, h0, taps, bias.view(1) if bias is not None else None, 'GCRNN_NO_SMALL_CLS_GNN_HEAD',
+                                       lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
+                                       lambda x: every or self._small_cls_gnn_head_pays(x, False),
+                                       lambda N, G, F, Kin, Kst, K_o, dt, backward, gated, dx=False:
+                                       ops.small_cls_gnn_head_supported(N, G, F, Kin, Kst, K_o, C, dt, backward, gated, dx=dx))
+        if route is None or (route[0] and not every and not self._small_cls_gnn_head_pays(X, True)):
+            return None
+        lin_grad = torch.is_grad_enabled() and (lin_weight.requires_grad or (lin_bias is not None and lin_bias.requires_grad))
+        if lin_grad and not route[0]:
+            return None             # only the read-out wants a gradient: the route has asked for an inference launch
+        return ops.small_cell_classify_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps,
+                                           bias.view(1) if bias is not None else None, lin_weight, lin_bias, act, route[1], route[2])
+
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----
     def _use_fused(self, X, h0):
         if self._wants_grad(X, h0):

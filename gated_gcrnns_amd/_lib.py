@@ -181,6 +181,9 @@ def _bind(lib):
         'gcrnn_small_dense_gnn_head_supported': (C.c_int, [C.c_int] + [_c_i64] * 6 + [C.c_int] * 3),
         'gcrnn_small_dense_forward_gnn_head': (C.c_int, [C.c_int] + [_c_p] * 12 + [_c_i64] * 11 + [C.c_int, C.c_int, _c_p]),
         'gcrnn_small_gnn_head_adjoint': (C.c_int, [C.c_int] + [_c_p] * 4 + [_c_i64] * 3 + [C.c_int, _c_p]),
+        'gcrnn_small_dense_cls_gnn_head_supported': (C.c_int, [C.c_int] + [_c_i64] * 7 + [C.c_int] * 3),
+        'gcrnn_small_dense_forward_cls_gnn_head': (C.c_int, [C.c_int] + [_c_p] * 15 + [_c_i64] * 12 + [C.c_int, C.c_int, _c_p]),
+        'gcrnn_small_dense_backward_cls_gnn_head': (C.c_int, [C.c_int] + [_c_p] * 21 + [_c_i64] * 12 + [C.c_int, _c_p]),
         'gcrnn_small_gates_supported': (C.c_int, [C.c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, C.c_int]),
         'gcrnn_small_gates_forward': (C.c_int, [C.c_int] + [_c_p] * 9 + [_c_i64] * 7 + [_c_p]),
         'gcrnn_small_gates_backward': (C.c_int, [C.c_int] + [_c_p] * 14 + [_c_i64] * 7 + [_c_p]),

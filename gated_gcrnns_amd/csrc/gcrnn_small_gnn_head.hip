@@ -10,13 +10,6 @@
 
 namespace {
 
-template <typename T> __device__ __forceinline__ T gnn_act_grad(T y, int act) {      // from the activation's OUTPUT, as the layer's own backward
-  if (act == 1) return y > T(0) ? T(1) : T(0);
-  if (act == 2) return T(1) - y * y;
-  if (act == 3) return y * (T(1) - y);
-  return T(1);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void gnn_head_adjoint_kernel(const T* __restrict__ dY,     // [items][N]
                                                                const T* __restrict__ Y,      // [items][N]

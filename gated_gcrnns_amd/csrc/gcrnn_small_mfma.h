@@ -41,6 +41,15 @@ __host__ __device__ inline int lds_stride(int n) {
 template <typename T>
 inline size_t gnn_adjoint_lds(int64_t N) { return sizeof(T) * ((size_t)N * (size_t)N + 8 * (size_t)N); }
 
+// derivative of the graph-filter layer's activations (codes of ops._GFL_ACTS) from the activation's OUTPUT, as the layer's own backward:
+// shared by the head's adjoint kernel (gcrnn_small_gnn_head.hip) and the BPTT launch's seeding from a graph-filter head on the last state
+template <typename T> __device__ __forceinline__ T gnn_act_grad(T y, int act) {
+  if (act == 1) return y > T(0) ? T(1) : T(0);
+  if (act == 2) return T(1) - y * y;
+  if (act == 3) return y * (T(1) - y);
+  return T(1);
+}
+
 // acc += sum over `ksteps` k-steps of A(i, k) B(k, j): ap / bp point at this lane's element of k-step 0 and advance by
 // astep / bstep elements per k-step. Branch-free (masked lanes point at a row of zeros) and batched by four so that
 // eight LDS reads are in flight before the dependent MFMA chain consumes them.

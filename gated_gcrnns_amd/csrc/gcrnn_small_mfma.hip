@@ -31,8 +31,11 @@ namespace {
 // head branch costs the MAXT = 4 instantiations scratch. MODE = FWD_GNN has the choice of stored states and a one-layer graph-filter head
 // on EVERY state: Y[b][t][0][n] = act(head_b + sum_{k < NC} sum_f head_w[k][f] (h_t S^k)[f][n]) (k ascending, f ascending), NC = K_o its
 // number of taps. (h_t S^k) are the state rows of hop level k of step t + 1, so the head shifts nothing of its own while K_o <= K; the
-// levels K .. K_o - 1 are shifted for the state rows alone into ZX, outside the rows the tap MFMAs read.
-enum { FWD_PLAIN = 0, FWD_LAST = 1, FWD_NODE = 2, FWD_GNN = 3 };
+// levels K .. K_o - 1 are shifted for the state rows alone into ZX, outside the rows the tap MFMAs read. MODE = FWD_CLS_GNN has the choice
+// of stored states and, on the LAST state only, that graph-filter head followed by a read-out Linear(N -> NL): v[n] = act(head_b + sum_k
+// sum_f head_w[k][f] (h_T S^k)[f][n]), logits[b][c] = lin_b[c] + sum_n lin_w[c][n] v[n] (the classification model's Selection-GNN head).
+// Its time loop is the plain one; the head is FWD_GNN's epilogue into an LDS vector and FWD_LAST's wave-per-class read-out over it.
+enum { FWD_PLAIN = 0, FWD_LAST = 1, FWD_NODE = 2, FWD_GNN = 3, FWD_CLS_GNN = 4 };
 
 // the graph-filter layer's activations in its codes (ops._GFL_ACTS): 0 identity, 1 ReLU, 2 tanh, 3 sigmoid
 template <typename T> __device__ __forceinline__ T dense_gnn_act(T v, int act) {
@@ -56,9 +59,13 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     int64_t gsb, int64_t gst, int64_t gsn,       // gate element (b, t, n) sits at b gsb + t gst + n gsn
     const T* __restrict__ head_w,  // [NC][F N] read-out on the last state (nn.Linear weight, row-major over (f, n)) or null | FWD_NODE, FWD_GNN: [NC][F]
     const T* __restrict__ head_b,  // [NC] or null | FWD_GNN: [1] or null
-    T* __restrict__ logits,        // [B][NC] (with head_w) | FWD_NODE: Y [B][Tn][NC][N] | FWD_GNN: Y [B][Tn][1][N]
+    T* __restrict__ logits,        // [B][NC] (with head_w) | FWD_NODE: Y [B][Tn][NC][N] | FWD_GNN: Y [B][Tn][1][N] | FWD_CLS_GNN: [B][NL]
     int NC, int store,             // store: GCRNN_SMALL_STATES_ALL / _LAST / _NONE
-    int act) {                     // FWD_GNN: the head's activation (dense_gnn_act)
+    int act,                       // FWD_GNN, FWD_CLS_GNN: the head's activation (dense_gnn_act)
+    const T* __restrict__ lin_w,   // FWD_CLS_GNN: [NL][N] the read-out behind the graph-filter head (the other modes ignore these four)
+    const T* __restrict__ lin_b,   //              [NL] or null
+    T* __restrict__ V,             //              [B][N] the head's output on the last state, or null (the training forward keeps it)
+    int NL) {
   constexpr bool EXT = MODE != FWD_PLAIN;
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
@@ -73,9 +80,10 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
   T* zrow = W + (size_t)F16 * KCs;                 // [Ns] zeros: what masked lanes read
   T* gvec = zrow + Ns;                             // [2][Ns] gates of this step: input-filter | state-filter, per node
   T* hw = gvec + 2 * Ns;                           // FWD_NODE: [NC][F + 1] the head's weights, its bias in column F (dense_node_head_lds)
-                                                   // FWD_GNN: [NC][F] the head's taps, then its bias (dense_gnn_head_lds)
+                                                   // FWD_GNN, FWD_CLS_GNN: [NC][F] the head's taps, then its bias (dense_gnn_head_lds)
   const int F4 = (F + 3) & ~3;
-  T* ZX = hw + ((NC * F + 1 + 3) & ~3);            // FWD_GNN: [NC - K][F4][Ns] state rows of the hop levels K .. NC - 1
+  T* ZX = hw + ((NC * F + 1 + 3) & ~3);            // FWD_GNN, FWD_CLS_GNN: [NC - K][F4][Ns] state rows of the hop levels K .. NC - 1
+  T* vv = ZX + (size_t)(NC > K ? NC - K : 0) * F4 * Ns;      // FWD_CLS_GNN: [Ns] the head's output on the last state (dense_cls_gnn_head_lds)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int b = blockIdx.x;
@@ -123,29 +131,31 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
       }
     }
   };
-  // FWD_GNN: y_t from the state rows of all NC levels, one thread per node taken from the END of the block as node_head's are. It reads
-  // the state rows only -- never the x rows of the same levels, which hold x_{t+1} by then -- and runs after the last hop barrier of step
-  // t + 1 and before the barrier behind that step's taps, where nothing writes those rows. From the bias, k ascending, f ascending.
+  // FWD_GNN: y_t from the state rows of all NC levels (gnn_node: one node's value; FWD_CLS_GNN uses it for the last state alone), one thread
+  // per node taken from the END of the block as node_head's are. It reads the state rows only -- never the x rows of the same levels, which
+  // hold x_{t+1} by then -- and runs after the last hop barrier of step t + 1 and before the barrier behind that step's taps, where nothing
+  // writes those rows. From the bias, k ascending, f ascending.
+  auto gnn_node = [&](int n) -> T {
+    T s = hw[NC * F];
+    for (int k = 0; k < NC; ++k) {
+      const T* wr = hw + k * F;
+      const T* zr = gnn_level(k) + n;
+      int f = 0;
+      for (; f + 4 <= F; f += 4) {
+        const T w0 = wr[f], w1 = wr[f + 1], w2 = wr[f + 2], w3 = wr[f + 3];
+        const T z0 = zr[f * Ns], z1 = zr[(f + 1) * Ns], z2 = zr[(f + 2) * Ns], z3 = zr[(f + 3) * Ns];
+        s += w0 * z0;
+        s += w1 * z1;
+        s += w2 * z2;
+        s += w3 * z3;
+      }
+      for (; f < F; ++f) s += wr[f] * zr[f * Ns];
+    }
+    return dense_gnn_act<T>(s, act);
+  };
   auto gnn_head = [&](int t) {
     T* yt = logits + ((size_t)b * Tn + t) * N;
-    for (int n = 1023 - tid; n < N; n += 1024) {
-      T s = hw[NC * F];
-      for (int k = 0; k < NC; ++k) {
-        const T* wr = hw + k * F;
-        const T* zr = gnn_level(k) + n;
-        int f = 0;
-        for (; f + 4 <= F; f += 4) {
-          const T w0 = wr[f], w1 = wr[f + 1], w2 = wr[f + 2], w3 = wr[f + 3];
-          const T z0 = zr[f * Ns], z1 = zr[(f + 1) * Ns], z2 = zr[(f + 2) * Ns], z3 = zr[(f + 3) * Ns];
-          s += w0 * z0;
-          s += w1 * z1;
-          s += w2 * z2;
-          s += w3 * z3;
-        }
-        for (; f < F; ++f) s += wr[f] * zr[f * Ns];
-      }
-      yt[n] = dense_gnn_act<T>(s, act);
-    }
+    for (int n = 1023 - tid; n < N; n += 1024) yt[n] = gnn_node(n);
   };
 
   for (int i = tid; i < N4 * Ns; i += 1024) {
@@ -154,7 +164,7 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
   }
   for (int i = tid; i < KC4 * Ns; i += 1024) Z[i] = T(0);
   for (int i = tid; i < 3 * Ns; i += 1024) zrow[i] = T(0);
-  if (MODE == FWD_GNN) {
+  if (MODE == FWD_GNN || MODE == FWD_CLS_GNN) {
     for (int i = tid; i <= NC * F; i += 1024) hw[i] = i < NC * F ? head_w[i] : (head_b ? head_b[0] : T(0));
     for (int i = tid; i < (NC > K ? NC - K : 0) * F4 * Ns; i += 1024) ZX[i] = T(0);
   }
@@ -293,6 +303,29 @@ __global__ __launch_bounds__(1024) void small_dense_fwd_kernel(
     }
     gnn_head(Tn - 1);
   }
+  if (MODE == FWD_CLS_GNN) {
+    // ---- graph-filter head and read-out on the last state: FWD_GNN's epilogue into vv, then FWD_LAST's read-out over it
+    __syncthreads();                    // the last state is in Z
+    for (int k = 1; k < NC; ++k) {
+      gnn_state_hop(k);
+      __syncthreads();
+    }
+    for (int n = 1023 - tid; n < N; n += 1024) {
+      const T v = gnn_node(n);
+      vv[n] = v;
+      if (V) V[(size_t)b * N + n] = v;
+    }
+    __syncthreads();
+    // logits[b][c] = lin_w[c] . v + lin_b[c]: one wave per class, lanes stride over n, fixed-order butterfly, lane 0 stores
+    for (int c = wave; c < NL; c += 16) {
+      const T* wr = lin_w + (size_t)c * N;
+      T s = T(0);
+      for (int n = lane; n < N; n += 64) s += wr[n] * vv[n];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (lane == 0) logits[(size_t)b * NL + c] = s + (lin_b ? lin_b[c] : T(0));
+    }
+  }
   if (MODE == FWD_LAST && head_w) {
     // ---- read-out on the last state (rows G .. G+F-1 of Z): logits[b][c] = head_w[c] . vec_{F,N}(h_T) + head_b[c].
     // One wave per class, lanes stride over f N + n (coalesced head_w rows), fixed-order butterfly, lane 0 stores.
@@ -345,7 +378,11 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
     const T* __restrict__ dlogits,  // dH == null, dY == null: the upstream gradient is that of a read-out on the last state, [B][NC]
     const T* __restrict__ head_w,   //             [NC][F N]   |   with dY: node_w [NC][F]
     int NC,
-    const T* __restrict__ dY) {     // dH == null: the upstream gradient is that of a per-node head on every state, [B][Tn][NC][N]
+    const T* __restrict__ dY,       // dH == null: the upstream gradient is that of a per-node head on every state, [B][Tn][NC][N]
+    T* __restrict__ dU,             // dH == null, dY == null, dU given: the upstream gradient is that of a graph-filter head + read-out on the
+                                    // last state: dlogits [B][NC], lin_w [NC][N], head_w the head's taps [Ko][F]; dU [B][Ko][N] is written
+    const T* __restrict__ lin_w, const T* __restrict__ V,     // V [B][N]: the head's output on the last state (the forward's)
+    int Ko, int act) {
   typedef typename Mf<T>::acc acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_dense[];
   const int K = Kin > Kst ? Kin : Kst;
@@ -415,7 +452,41 @@ __global__ __launch_bounds__(1024) void small_dense_bwd_kernel(
   for (int q = 0; q < MAXW; ++q) wacc[q] = acc_t{0, 0, 0, 0};
   T bacc = T(0);
   const int FN = F * N, GN = G * N;
-  if (!dH && !dY) {
+  if (!dH && !dY && dU) {
+    // graph-filter head + read-out upstream (the classification model's Selection-GNN head): dH_t exists at t = Tn-1 only,
+    //   dv[n] = sum_c dlogits[b][c] lin_w[c][n] (c ascending),  dU_0 = dv . act'(V),  dU_k[m] = sum_n dU_{k-1}[n] S[m][n] (n ascending),
+    //   dH_T[f][n] = sum_k head_w[k][f] dU_k[n] (k ascending) -> the carry tile, as for the read-out below. Once per sequence: one thread per
+    // node. The two levels in flight borrow columns 0 .. N-1 of rows 0 and 1 of Z0 (C >= 2), which the first step's copy of x_t | h_{t-1}
+    // overwrites before anything reads them; the padding columns are not touched. Every element of dU[b] is written.
+    T* u0 = Z0;
+    T* u1 = Z0 + Ns;
+    T* dub = dU + (size_t)b * Ko * N;
+    for (int n = tid; n < N; n += 1024) {
+      T s = T(0);
+      for (int c = 0; c < NC; ++c) s += dlogits[(size_t)b * NC + c] * lin_w[(size_t)c * N + n];
+      const T d = s * gnn_act_grad<T>(V[(size_t)b * N + n], act);
+      u0[n] = d;
+      dub[n] = d;
+    }
+    __syncthreads();
+    for (int k = 0; k < Ko; ++k) {
+      for (int i = tid; i < FN; i += 1024) {
+        const int f = i / N, n = i - f * N;
+        const T p = head_w[(size_t)k * F + f] * u0[n];
+        carry[f * Ns + n] = k ? carry[f * Ns + n] + p : p;
+      }
+      if (k + 1 < Ko)
+        for (int m = tid; m < N; m += 1024) {
+          const T* sr = S + (size_t)m * Ns;
+          T s = T(0);
+          for (int n = 0; n < N; ++n) s += u0[n] * sr[n];
+          u1[m] = s;
+          dub[(size_t)(k + 1) * N + m] = s;
+        }
+      __syncthreads();
+      T* tmp = u0; u0 = u1; u1 = tmp;
+    }
+  } else if (!dH && !dY) {
     // read-out upstream: dH_t exists at t = Tn-1 only, dH_T[f][n] = sum_c dlogits[b][c] head_w[c][f N + n] (c ascending). It starts
     // in the carry tile, so every step below sees "no dH_t" and no dH is allocated, zero-filled or read.
     for (int i = tid; i < FN; i += 1024) {
@@ -672,6 +743,12 @@ size_t dense_gnn_head_lds(int64_t N, int64_t F, int64_t K, int64_t Ko) {
   return sizeof(T) * ((size_t)((Ko * F + 1 + 3) & ~(int64_t)3) + (Ko > K ? (size_t)(Ko - K) * F4 * Ns : 0));
 }
 
+// the graph-filter head followed by a read-out on the last state: the graph-filter head's share and its output vector v [Ns]
+template <typename T>
+size_t dense_cls_gnn_head_lds(int64_t N, int64_t F, int64_t K, int64_t Ko) {
+  return dense_gnn_head_lds<T>(N, F, K, Ko) + sizeof(T) * (size_t)lds_stride<T>((int)N);
+}
+
 constexpr size_t DENSE_LDS_MAX = 160 * 1024;
 
 template <typename T>
@@ -720,10 +797,13 @@ struct DenseFwdArgs {
   int64_t NC = 0;
   int store = GCRNN_SMALL_STATES_ALL;
   int act = 0;                     // FWD_GNN: head_w [NC][F] the head's taps, head_b [1], out = Y [B][T][1][N], NC = K_o
+  const void *lin_w = nullptr, *lin_b = nullptr;      // FWD_CLS_GNN: FWD_GNN's head on the last state, then lin_w [NL][N], lin_b [NL];
+  void* V = nullptr;                                  // out = logits [B][NL], V [B][N] the head's output or null
+  int64_t NL = 0;
 };
 
 // One BPTT launch. The upstream gradient: dH [B][T][F][N]; or dlogits [B][NC] with head_w [NC][F N] (read-out on the last state); or
-// dY [B][T][NC][N] with head_w = node_w [NC][F] (per-node head). dX == nullptr selects the plain variant.
+// dY [B][T][NC][N] with head_w = node_w [NC][F] (per-node head); or dU (below). dX == nullptr selects the plain variant.
 struct DenseBwdArgs {
   const void *X, *h0, *H, *wA, *wB, *bias, *gi, *gf, *Sd;
   void *pA, *pB, *pb, *dgi, *dgf, *dh0, *dX;
@@ -731,6 +811,10 @@ struct DenseBwdArgs {
   hipStream_t st;
   const void *dH = nullptr, *dlogits = nullptr, *dY = nullptr, *head_w = nullptr;
   int64_t NC = 0;
+  void* dU = nullptr;              // graph-filter head + read-out on the last state: dlogits [B][NC], lin_w [NC][N], V [B][N], head_w
+  const void *lin_w = nullptr, *V = nullptr;      // [Ko][F] the head's taps, dU [B][Ko][N] written by the launch
+  int64_t Ko = 0;
+  int act = 0;
 };
 
 // What the entries share, in the order they ask it: a gate comes with its partner and, in a backward pass (want_dg), with room for both
@@ -746,9 +830,11 @@ template <typename T>
 static int dense_fwd_launch(const DenseFwdArgs& a, int mode) {
   const int64_t N = a.N, F = a.F, K = a.Kin > a.Kst ? a.Kin : a.Kst;
   const size_t lds = dense_fwd_lds<T>(N, a.G, F, K) + (mode == FWD_NODE ? dense_node_head_lds<T>(F, a.NC) : 0) +
-                     (mode == FWD_GNN ? dense_gnn_head_lds<T>(N, F, K, a.NC) : 0);
+                     (mode == FWD_GNN ? dense_gnn_head_lds<T>(N, F, K, a.NC) : 0) +
+                     (mode == FWD_CLS_GNN ? dense_cls_gnn_head_lds<T>(N, F, K, a.NC) : 0);
   const int64_t ot = ((F + 15) / 16) * ((N + 15) / 16);             // output tiles per step, dealt over 16 waves
-  auto kern = mode == FWD_GNN ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_GNN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_GNN> : small_dense_fwd_kernel<T, 4, FWD_GNN>))
+  auto kern = mode == FWD_CLS_GNN ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_CLS_GNN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_CLS_GNN> : small_dense_fwd_kernel<T, 4, FWD_CLS_GNN>))
+              : mode == FWD_GNN ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_GNN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_GNN> : small_dense_fwd_kernel<T, 4, FWD_GNN>))
               : mode == FWD_NODE ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_NODE> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_NODE> : small_dense_fwd_kernel<T, 4, FWD_NODE>))
               : mode == FWD_LAST ? (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_LAST> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_LAST> : small_dense_fwd_kernel<T, 4, FWD_LAST>))
                                  : (ot <= 16 ? small_dense_fwd_kernel<T, 1, FWD_PLAIN> : (ot <= 32 ? small_dense_fwd_kernel<T, 2, FWD_PLAIN> : small_dense_fwd_kernel<T, 4, FWD_PLAIN>));
@@ -757,12 +843,13 @@ static int dense_fwd_launch(const DenseFwdArgs& a, int mode) {
   GCRNN_PRE_LAUNCH();
   kern<<<(unsigned)a.B, 1024, lds, a.st>>>((const T*)a.X, (const T*)a.h0, (const T*)a.wA, (const T*)a.wB, (const T*)a.bias, (const T*)a.gi,
                                           (const T*)a.gf, (const T*)a.Sd, (T*)a.H, (int)a.T, (int)N, (int)a.G, (int)F, (int)a.Kin, (int)a.Kst,
-                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.head_w, (const T*)a.head_b, (T*)a.out, (int)a.NC, a.store, a.act);
+                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.head_w, (const T*)a.head_b, (T*)a.out, (int)a.NC, a.store, a.act,
+                                          (const T*)a.lin_w, (const T*)a.lin_b, (T*)a.V, (int)a.NL);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
 
-// The one place that picks the forward instantiation: <T> here, MAXT and the mode (FWD_PLAIN / FWD_LAST / FWD_NODE / FWD_GNN) in the launcher.
+// The one place that picks the forward instantiation: <T> here, MAXT and the mode (FWD_PLAIN / FWD_LAST / FWD_NODE / FWD_GNN / FWD_CLS_GNN) in the launcher.
 static int dense_fwd_run(int dtype, const DenseFwdArgs& a, int mode) {
   return dtype == GCRNN_F32 ? dense_fwd_launch<float>(a, mode) : dense_fwd_launch<double>(a, mode);
 }
@@ -794,7 +881,8 @@ static int dense_bwd_launch(const DenseBwdArgs& a) {
   kern<<<(unsigned)a.B, 1024, lds, a.st>>>((const T*)a.X, (const T*)a.h0, (const T*)a.H, (const T*)a.dH, (const T*)a.wA, (const T*)a.wB,
                                           (const T*)a.bias, (const T*)a.gi, (const T*)a.gf, (const T*)a.Sd, (T*)a.pA, (T*)a.pB, (T*)a.pb,
                                           (T*)a.dgi, (T*)a.dgf, (T*)a.dh0, (T*)a.dX, (int)a.T, (int)N, (int)G, (int)F, (int)Kin, (int)Kst,
-                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.dlogits, (const T*)a.head_w, (int)a.NC, (const T*)a.dY);
+                                          (int)a.B, a.gsb, a.gst, a.gsn, (const T*)a.dlogits, (const T*)a.head_w, (int)a.NC, (const T*)a.dY,
+                                          (T*)a.dU, (const T*)a.lin_w, (const T*)a.V, (int)a.Ko, a.act);
   GCRNN_CHECK_LAUNCH();
   return GCRNN_OK;
 }
@@ -983,4 +1071,66 @@ extern "C" int gcrnn_small_dense_forward_gnn_head(int dtype, const void* X, cons
                        .G = G, .F = F, .Kin = Kin, .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n,
                        .st = as_stream(stream), .head_w = head_w, .head_b = head_b, .out = Y, .NC = Ko, .store = store_states, .act = act};
   return dense_fwd_run(dtype, a, FWD_GNN);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// one-layer graph-filter head + read-out Linear(N -> C) on the LAST state (the classification model's Selection-GNN head, GraphFilter(F -> 1,
+// K_o) + activation, then nn.Linear): logits from the forward launch (FWD_CLS_GNN), BPTT seeded from dlogits inside its launch, which also
+// writes the head's adjoint levels dU [B][K_o][N] for the parameter gradients
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int gcrnn_small_dense_cls_gnn_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t Ko,
+                                                        int64_t C, int backward, int gated, int dx) {
+  if (Ko <= 0 || Ko > GCRNN_SMALL_NODE_HEAD_MAX_OUT || C <= 0 || C > GCRNN_SMALL_HEAD_MAX_CLASSES) return 0;
+  if (!gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated)) return 0;
+  if (dx && !gcrnn_small_dense_backward_dx_supported(dtype, N, G, F, Kin, Kst, gated)) return 0;
+  if (backward) return 1;               // the seeding borrows two rows of the BPTT launch's own Z tile: the LDS image of the plain backward
+  const int64_t K = Kin > Kst ? Kin : Kst;
+  const size_t lds = dtype == GCRNN_F32 ? dense_fwd_lds<float>(N, G, F, K) + dense_cls_gnn_head_lds<float>(N, F, K, Ko)
+                                        : dense_fwd_lds<double>(N, G, F, K) + dense_cls_gnn_head_lds<double>(N, F, K, Ko);
+  return lds <= DENSE_LDS_MAX ? 1 : 0;
+}
+
+extern "C" int gcrnn_small_dense_forward_cls_gnn_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB,
+                                                      const void* bias, const void* gi, const void* gf, const void* Sdense,
+                                                      const void* head_w, const void* head_b, const void* lin_w, const void* lin_b,
+                                                      void* H, void* V, void* logits, int64_t B, int64_t T, int64_t N, int64_t G,
+                                                      int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t,
+                                                      int64_t gate_stride_n, int64_t Ko, int64_t C, int act, int store_states,
+                                                      void* stream) {
+  if (!X || !h0 || !wA || !wB || !Sdense || !head_w || !lin_w || !logits) return GCRNN_ERR_NULL_POINTER;
+  if (int s = dense_shared_status(gi, gf, false, nullptr, nullptr, true, dtype)) return s;
+  if (store_states != GCRNN_SMALL_STATES_ALL && store_states != GCRNN_SMALL_STATES_LAST && store_states != GCRNN_SMALL_STATES_NONE)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (store_states != GCRNN_SMALL_STATES_NONE && !H) return GCRNN_ERR_NULL_POINTER;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (Ko <= 0 || Ko > GCRNN_SMALL_NODE_HEAD_MAX_OUT || C <= 0 || C > GCRNN_SMALL_HEAD_MAX_CLASSES || act < 0 || act > 3)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_cls_gnn_head_supported(dtype, N, G, F, Kin, Kst, Ko, C, 0, gi != nullptr, 0)) return GCRNN_ERR_UNSUPPORTED;
+  // the training forward stores the states of the forward-only image; its backward is asked separately
+  const DenseFwdArgs a{.X = X, .h0 = h0, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .H = H, .B = B, .T = T, .N = N,
+                       .G = G, .F = F, .Kin = Kin, .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n,
+                       .st = as_stream(stream), .head_w = head_w, .head_b = head_b, .out = logits, .NC = Ko, .store = store_states, .act = act,
+                       .lin_w = lin_w, .lin_b = lin_b, .V = V, .NL = C};
+  return dense_fwd_run(dtype, a, FWD_CLS_GNN);
+}
+
+extern "C" int gcrnn_small_dense_backward_cls_gnn_head(int dtype, const void* X, const void* h0, const void* H, const void* dlogits,
+                                                       const void* lin_w, const void* V, const void* head_w, const void* wA,
+                                                       const void* wB, const void* bias, const void* gi, const void* gf,
+                                                       const void* Sdense, void* pA, void* pB, void* pb, void* dgi, void* dgf, void* dh0,
+                                                       void* dX, void* dU, int64_t B, int64_t T, int64_t N, int64_t G, int64_t F,
+                                                       int64_t Kin, int64_t Kst, int64_t gate_stride_b, int64_t gate_stride_t,
+                                                       int64_t gate_stride_n, int64_t Ko, int64_t C, int act, void* stream) {
+  if (!X || !h0 || !H || !dlogits || !lin_w || !V || !head_w || !wA || !wB || !Sdense || !pA || !pB || !pb || !dU)
+    return GCRNN_ERR_NULL_POINTER;
+  if (int s = dense_shared_status(gi, gf, true, dgi, dgf, true, dtype)) return s;
+  if (!dense_bt_ok(B, T) || N <= 0 || G <= 0 || F <= 0 || Kin <= 0 || Kst <= 0) return GCRNN_ERR_BAD_SHAPE;
+  if (Ko <= 0 || Ko > GCRNN_SMALL_NODE_HEAD_MAX_OUT || C <= 0 || C > GCRNN_SMALL_HEAD_MAX_CLASSES || act < 0 || act > 3)
+    return GCRNN_ERR_BAD_SHAPE;
+  if (!gcrnn_small_dense_cls_gnn_head_supported(dtype, N, G, F, Kin, Kst, Ko, C, 1, gi != nullptr, dX != nullptr)) return GCRNN_ERR_UNSUPPORTED;
+  const DenseBwdArgs a{.X = X, .h0 = h0, .H = H, .wA = wA, .wB = wB, .bias = bias, .gi = gi, .gf = gf, .Sd = Sdense, .pA = pA, .pB = pB,
+                       .pb = pb, .dgi = dgi, .dgf = dgf, .dh0 = dh0, .dX = dX, .B = B, .T = T, .N = N, .G = G, .F = F, .Kin = Kin,
+                       .Kst = Kst, .gsb = gate_stride_b, .gst = gate_stride_t, .gsn = gate_stride_n, .st = as_stream(stream),
+                       .dlogits = dlogits, .head_w = head_w, .NC = C, .dU = dU, .lin_w = lin_w, .V = V, .Ko = Ko, .act = act};
+  return dense_bwd_run(dtype, a);
 }

@@ -2994,10 +2994,12 @@ def _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, head=None):
     """The one forward launch of the matrix-core family: the recurrence, the states `store` asks for and the output of `head`. head: None,
     ('last', head_w [C][F N], head_b [C] or None) -- the read-out on the last state, logits [B][C] -- or ('node', node_w [O][F], node_b [O] or
     None) -- the per-node head on every state, Y [B][T][O][N] -- or ('gnn', head_w [K_o][F], head_b [1] or None, act) -- the one-layer
-    graph-filter head on every state, Y [B][T][1][N], act a key of _GFL_ACTS. Returns (H or None, logits / Y or None). Entry point: no head
+    graph-filter head on every state, Y [B][T][1][N], act a key of _GFL_ACTS -- or ('cls_gnn', head_w [K_o][F], head_b [1] or None, act,
+    lin_w [C][N], lin_b [C] or None, V [B][N] to fill or None) -- that graph-filter head on the last state and a read-out Linear(N -> C)
+    behind it, logits [B][C]. Returns (H or None, logits / Y or None). Entry point: no head
     and every state gcrnn_small_dense_forward; no head and the last state gcrnn_small_dense_forward_head without a read-out; 'last' the
-    same entry with one; 'node' gcrnn_small_dense_forward_node_head; 'gnn' gcrnn_small_dense_forward_gnn_head. Every operand stays a local
-    of this frame up to the launch (_small_dense_bptt)."""
+    same entry with one; 'node' gcrnn_small_dense_forward_node_head; 'gnn' gcrnn_small_dense_forward_gnn_head; 'cls_gnn'
+    gcrnn_small_dense_forward_cls_gnn_head. Every operand stays a local of this frame up to the launch (_small_dense_bptt)."""
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
     dt, dev = X.dtype, X.device
@@ -3008,10 +3010,19 @@ def _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, head=None):
     if head is not None:
         NC = hw.shape[0]
         assert tuple(hw.shape) == ((NC, F * N) if kind == 'last' else (NC, F)) and hw.dtype == dt
-        assert hb is None or (hb.dtype == dt and hb.numel() == (1 if kind == 'gnn' else NC))
-        out = torch.empty((B, NC) if kind == 'last' else (B, T, 1 if kind == 'gnn' else NC, N), dtype=dt, device=dev)
+        assert hb is None or (hb.dtype == dt and hb.numel() == (1 if kind in ('gnn', 'cls_gnn') else NC))
         hw = hw.detach().contiguous()
         hb = hb.detach().contiguous() if hb is not None else None
+        if kind == 'cls_gnn':
+            lw, lb, V = head[4:7]
+            NL = lw.shape[0]
+            assert tuple(lw.shape) == (NL, N) and lw.dtype == dt and (lb is None or (lb.dtype == dt and lb.numel() == NL))
+            assert V is None or (V.is_contiguous() and V.dtype == dt and tuple(V.shape) == (B, N))
+            lw = lw.detach().contiguous()
+            lb = lb.detach().contiguous() if lb is not None else None
+            out = torch.empty((B, NL), dtype=dt, device=dev)
+        else:
+            out = torch.empty((B, NC) if kind == 'last' else (B, T, 1 if kind == 'gnn' else NC, N), dtype=dt, device=dev)
     bvec = bias.detach().contiguous().view(-1) if bias is not None else None
     if gi is not None:
         gi, gf = gi.detach().to(dt).contiguous(), gf.detach().to(dt).contiguous()
@@ -3024,6 +3035,9 @@ def _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, head=None):
     if head is None and store == SMALL_STATES_ALL:
         name = 'small_dense_forward'
         args += (_p(H),) + dims
+    elif kind == 'cls_gnn':
+        name = 'small_dense_forward_cls_gnn_head'
+        args += (_p(hw), _p(hb), _p(lw), _p(lb), _p(H), _p(V), _p(out)) + dims + (NC, NL, _GFL_ACTS[head[3]], store)
     else:
         name = {'node': 'small_dense_forward_node_head', 'gnn': 'small_dense_forward_gnn_head'}.get(kind, 'small_dense_forward_head')
         args += (_p(hw), _p(hb), _p(H), _p(out)) + dims + ((NC, _GFL_ACTS[head[3]], store) if kind == 'gnn' else (NC, store))
@@ -3131,13 +3145,16 @@ def _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, graph, want_dx, want_dh0, 
     """The one BPTT launch of the matrix-core family and its reductions, from the tensors the forward saved. seed: the upstream gradient
     (kind, gradient, head weight), each contiguous: ('dH', dH [B][T][F][N], None), ('dlogits', dlogits [B][C], head_w [C][F N]) -- the
     read-out on the last state -- or ('dY', dY [B][T][O][N], node_w [O][F]) -- the per-node head; for the last two the kernel forms dH
-    itself. Entry point: 'dH' gcrnn_small_dense_backward, or gcrnn_small_dense_backward_dx with want_dx; 'dlogits'
-    gcrnn_small_dense_backward_head and 'dY' gcrnn_small_dense_backward_node_head, either with dX or NULL. The caller has asked whether the
+    itself; or ('dcls', dlogits [B][C], head_w [K_o][F], lin_w [C][N], V [B][N], act, dU [B][K_o][N]) -- the graph-filter head and read-out
+    on the last state: the kernel forms dH_T from dlogits, lin_w, the forward's V and the head's taps, and fills the caller's dU.
+    Entry point: 'dH' gcrnn_small_dense_backward, or gcrnn_small_dense_backward_dx with want_dx; 'dlogits'
+    gcrnn_small_dense_backward_head and 'dY' gcrnn_small_dense_backward_node_head, 'dcls' gcrnn_small_dense_backward_cls_gnn_head, each
+    with dX or NULL. The caller has asked whether the
     shape has a dx variant. Returns (dX, dh0, dwA, dwB, db, dgi, dgf); the gradients of a head's own parameters are the caller's.
 
     Every operand is a named local of this frame up to the launch: a temporary (wA.contiguous(), a first-use graph.dense(dt)) would be
     released -- and its block handed to the next allocation -- before the launch."""
-    kind, g, hw = seed
+    kind, g, hw = seed[:3]
     B, T, G, N = X.shape
     F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
     dt, dev = X.dtype, X.device
@@ -3161,6 +3178,11 @@ def _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, graph, want_dx, want_dh0, 
     if kind == 'dH':
         name = 'small_dense_backward_dx' if want_dx else 'small_dense_backward'
         args = cell + ((_p(dX),) if want_dx else ()) + dims
+    elif kind == 'dcls':
+        lw, V, act, dU = seed[3:]
+        assert lw.is_contiguous() and V.is_contiguous() and dU.is_contiguous() and tuple(dU.shape) == (B, hw.shape[0], N)
+        name = 'small_dense_backward_cls_gnn_head'
+        args = (_p(lw), _p(V), _p(hw)) + cell + (_p(dX), _p(dU)) + dims + (hw.shape[0], lw.shape[0], _GFL_ACTS[act])
     else:
         name = 'small_dense_backward_head' if kind == 'dlogits' else 'small_dense_backward_node_head'
         args = (_p(hw),) + cell + (_p(dX),) + dims + (hw.shape[0],)
@@ -3395,6 +3417,90 @@ def small_cell_regress_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, act=None,
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
         return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('gnn', head_w, head_b, act))[1]
     return _SmallCellGnnHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph, act)
+
+
+# ---- the classification model's Selection-GNN head on the matrix-core kernels: GraphFilter(F -> 1, K_o) + activation + Linear(N -> C) on
+# the last state inside the forward launch; the BPTT launch seeds itself from dlogits and writes the head's adjoint levels dU
+def small_cls_gnn_head_supported(N, G, F, Kin, Kst, K_o, C, dtype, backward, gated, dx=False, E=1):
+    """The matrix-core small-graph kernels take this cell with a one-layer graph-filter head of K_o taps and one output feature on its
+    last state and a read-out of C classes behind it (gcrnn_small_dense_cls_gnn_head_supported; E = 1, fp32 / fp64; GCRNN_SMALL_GATHER=1
+    answers no, as for small_dense_supported). backward: the training step, i.e. the forward launch with the head's LDS share and the
+    BPTT launch."""
+    if E != 1 or not small_dense_supported(N, G, F, Kin, Kst, dtype, backward, gated):
+        return False
+    shape = (dtype_code(dtype), int(N), int(G), int(F), int(Kin), int(Kst), int(K_o), int(C))
+    if not lib.gcrnn_small_dense_cls_gnn_head_supported(*shape, 0, int(bool(gated)), 0):
+        return False
+    return not backward or bool(lib.gcrnn_small_dense_cls_gnn_head_supported(*shape, 1, int(bool(gated)), int(bool(dx))))
+
+
+class _SmallCellClsGnnHead(torch.autograd.Function):
+    """Small-graph cell + GraphFilter(F -> 1, K_o) + activation + Linear(N -> C) on its last state as ONE autograd node. Forward: one
+    launch that stores every state (BPTT reads them), the head's output V [B][N] and the logits. Backward: one BPTT launch seeded from
+    dlogits inside the kernel (gcrnn_small_dense_backward_cls_gnn_head: no dH [B][T][F][N] and no buffer with a T in its shape is
+    allocated, and no adjoint kernel runs), which also writes dU [B][K_o][N]; the head's own parameters take library products of
+    dlogits, V, dU and the last state. No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, X, h0, wA, wB, bias, gi, gf, head_w, head_b, lin_w, lin_b, graph, act):
+        X, h0 = X.contiguous(), h0.contiguous()
+        V = torch.empty((X.shape[0], X.shape[3]), dtype=X.dtype, device=X.device)
+        H, logits = _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_ALL, ('cls_gnn', head_w, head_b, act, lin_w, lin_b, V))
+        ctx.save_for_backward(X, h0, H, wA, wB, bias, gi, gf, head_w, lin_w, V)
+        ctx.graph, ctx.has_hb, ctx.has_lb, ctx.act = graph, head_b is not None, lin_b is not None, act
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        X, h0, H, wA, wB, bias, gi, gf, head_w, lin_w, V = ctx.saved_tensors
+        B, T, G, N = X.shape
+        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        Ko, C = head_w.shape[0], lin_w.shape[0]
+        dt, dev = X.dtype, X.device
+        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_dx and not small_cls_gnn_head_supported(N, G, F, Kin, Kst, Ko, C, dt, True, gi is not None, dx=True):
+            raise GcrnnError('small_cell_classify_gnn: no gradient for X at this shape (small_cls_gnn_head_supported with dx)')
+        dlc, hw, lw = dlogits.to(dt).contiguous(), head_w.detach().contiguous(), lin_w.detach().contiguous()
+        dU = torch.empty((B, Ko, N), dtype=dt, device=dev)
+        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dcls', dlc, hw, lw, V, ctx.act, dU))
+        # d head_w[k][f] = sum_{b,n} dU[b][k][n] h_T[b][f][n] and d head_b = sum dU_0: the per-node head's sums with O = K_o on B items,
+        # through node_linear's backward kernel with dh = NULL on a contiguous copy of the last state ([B][F][N]; no buffer with a T in its
+        # shape). An einsum here is ONE fp64 GEMM of 4 x 20 outputs over a contraction of B N = 5900 -- a single serial tile, measured at
+        # 0.13 ms of device time per step (DESIGN 4.16). d lin_w = dlogits^T V, d lin_b its column sums, as the MLP heads everywhere
+        dhw = dhb = None
+        want_hb = ctx.has_hb and ctx.needs_input_grad[8]
+        if (ctx.needs_input_grad[7] or want_hb) and node_linear_supported(F, Ko, dt):
+            hT = H[:, -1].contiguous()
+            nblk = int(lib.gcrnn_node_linear_blocks(B, N))
+            pw = torch.empty((nblk, Ko, F), dtype=dt, device=dev)
+            pnb = torch.empty((nblk, Ko), dtype=dt, device=dev)
+            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(hT), _p(hw), _p(dU), None, _p(pw), _p(pnb), B, N, F, Ko, _stream()),
+                  'node_linear_backward')
+            dhw = pw.sum(dim=0) if ctx.needs_input_grad[7] else None
+            dhb = pnb[:, 0].sum(dim=0).view(1) if want_hb else None
+        else:
+            if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B][K_o][F] its only temporary
+                dhw = torch.bmm(dU, H[:, -1].transpose(1, 2)).sum(0)
+            dhb = dU[:, 0].sum().view(1) if want_hb else None
+        dlw = dlc.t().mm(V) if ctx.needs_input_grad[9] else None
+        dlb = dlc.sum(dim=0) if ctx.has_lb and ctx.needs_input_grad[10] else None
+        return grads + (dhw, dhb, dlw, dlb, None, None)
+
+
+def small_cell_classify_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, lin_w, lin_b, act=None, gi=None, gf=None):
+    """The small-graph cell followed, on its last state, by one graph-filter layer of K_o taps and one output feature and a
+    Linear(N -> C) (head_w [K_o][F] = GraphFilter.weight[0, 0], head_b [1] or None, lin_w [C][N], lin_b [C] or None, the states' dtype;
+    act in (None, 'relu', 'tanh', 'sigmoid')): logits[b] = lin_w act(sum_k head_w[k] (h_T S^k) + head_b) + lin_b, [B][C] -- the values
+    ops.graph_filter_layer and nn.Linear give on the cell's last state, in another summation order. Where nothing wants a gradient it
+    is one launch that stores no state; otherwise one autograd node (_SmallCellClsGnnHead) with gradients for X (only where wanted:
+    small_cls_gnn_head_supported with dx), h0, the taps, the bias, the gates and the head. Shapes: small_cls_gnn_head_supported."""
+    assert act in _GFL_ACTS, act
+    require_device(X, h0, wA, wB, bias, head_w, lin_w)
+    operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b, lin_w, lin_b)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
+        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE,
+                                    ('cls_gnn', head_w, head_b, act, lin_w, lin_b, None))[1]
+    return _SmallCellClsGnnHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, lin_w, lin_b, graph, act)
 
 
 def small_gates_supported(N, G, F, Kin, Kst, dtype, backward):

@@ -873,6 +873,45 @@ int gcrnn_small_dense_forward_gnn_head(int dtype, const void* X, const void* h0,
 int gcrnn_small_gnn_head_adjoint(int dtype, const void* dY, const void* Y, const void* Sdense, void* dU, int64_t items, int64_t N,
                                  int64_t K_o, int act, void* stream);
 
+/* The same two kernels with that graph-filter head on the LAST state only and a read-out behind it (the classification model's
+ * Selection-GNN head with dimNodeSignals = [F, 1], nFilterTaps = [K_o], NoPool and dimLayersMLP = [C], reference architectures.py:1823-1849).
+ *   head_w [K_o][F] (GraphFilter.weight[0, 0]), head_b [1] or NULL, lin_w [C][N] (nn.Linear weight), lin_b [C] or NULL, V [B][N],
+ *   logits / dlogits [B][C], dU [B][K_o][N], all of `dtype`; act in the layer's codes (0 identity, 1 ReLU, 2 tanh, 3 sigmoid):
+ *     v[b][n]      = act( head_b + sum_{k < K_o} sum_f head_w[k][f] (h_T S^k)[f][n] )      (from head_b, k ascending, f ascending)
+ *     logits[b][c] = lin_b[c] + sum_n lin_w[c][n] v[b][n]                                  (one wave per class, fixed order, no atomics)
+ * gcrnn_small_dense_forward_cls_gnn_head: the time loop is the plain recurrence's; behind it the last state's K_o - 1 levels are shifted
+ *   for the state rows alone, v goes to LDS -- and to V where V is not NULL: the training forward keeps it for the backward -- and the
+ *   read-out runs over it. Two runs give the same bits. store_states as above: _ALL for the training forward (H bit-identical to
+ *   gcrnn_small_dense_forward), _NONE for inference (H may be NULL: no state is ever stored), _LAST H [B][1][F][N].
+ * gcrnn_small_dense_backward_cls_gnn_head: BPTT whose only upstream gradient is dlogits. Inside the launch, once per sequence,
+ *     dv[n] = sum_c dlogits[b][c] lin_w[c][n] (c ascending),   dU_0 = dv . act'(V),   dU_k[m] = sum_n dU_{k-1}[n] Sdense[m][n] (n ascending),
+ *     dH_T[f][n] = sum_k head_w[k][f] dU_k[n] (k ascending)
+ *   seed the carried adjoint, so no dH [B][T][F][N] and no adjoint launch exist. dU is a side output, every element written. Other
+ *   arguments and results as gcrnn_small_dense_backward; dX [B][T][G][N] or NULL selects the dx variant. The gradients of the head's
+ *   own parameters are the caller's: d lin_w = dlogits^T V, d lin_b the column sums of dlogits, d head_w[k][f] = sum_{b,n} h_T[b][f][n]
+ *   dU[b][k][n], d head_b = sum dU[:, 0, :].
+ * gcrnn_small_dense_cls_gnn_head_supported: 1 <= K_o <= GCRNN_SMALL_NODE_HEAD_MAX_OUT, 1 <= C <= GCRNN_SMALL_HEAD_MAX_CLASSES and
+ *   gcrnn_small_dense_supported(dtype, N, G, F, Kin, Kst, backward, gated); with dx also gcrnn_small_dense_backward_dx_supported.
+ *   backward = 0 also asks that the forward's LDS image with the head's K_o F + 1 values, the extra levels' state rows where
+ *   K_o > max(Kin, Kst) and the vector v fits; the backward's seeding borrows two rows of a tile the launch has anyway (a training step
+ *   asks both). Answers without a device.
+ * Checked before any launch, in this order: GCRNN_ERR_NULL_POINTER, GCRNN_ERR_BAD_DTYPE, GCRNN_ERR_BAD_SHAPE (also an unknown
+ * store_states or act, K_o or C <= 0 or above its maximum), GCRNN_ERR_UNSUPPORTED where the query says no. */
+int gcrnn_small_dense_cls_gnn_head_supported(int dtype, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t K_o,
+                                             int64_t C, int backward, int gated, int dx);
+int gcrnn_small_dense_forward_cls_gnn_head(int dtype, const void* X, const void* h0, const void* wA, const void* wB, const void* bias,
+                                           const void* gi, const void* gf, const void* Sdense, const void* head_w,
+                                           const void* head_b, const void* lin_w, const void* lin_b, void* H, void* V, void* logits,
+                                           int64_t B, int64_t T, int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst,
+                                           int64_t gate_stride_b, int64_t gate_stride_t, int64_t gate_stride_n, int64_t K_o, int64_t C,
+                                           int act, int store_states, void* stream);
+int gcrnn_small_dense_backward_cls_gnn_head(int dtype, const void* X, const void* h0, const void* H, const void* dlogits,
+                                            const void* lin_w, const void* V, const void* head_w, const void* wA, const void* wB,
+                                            const void* bias, const void* gi, const void* gf, const void* Sdense, void* pA, void* pB,
+                                            void* pb, void* dgi, void* dgf, void* dh0, void* dX, void* dU, int64_t B, int64_t T,
+                                            int64_t N, int64_t G, int64_t F, int64_t Kin, int64_t Kst, int64_t gate_stride_b,
+                                            int64_t gate_stride_t, int64_t gate_stride_n, int64_t K_o, int64_t C, int act, void* stream);
+
 /* Time gates of the small-graph regime (GGCRNNCell time gating, graphML.py:2248-2278, 2357-2374), both gates in one launch:
  *   gate[g][t][b] = sigmoid( lw_g . vec_{F,N}( tanh(A_g(S) x_t + B_g(S) h0 + 2 b_g) ) + lb_g ),  g = 0 input, 1 forget.
  * Parameters stacked over the two gates: wA2 [2][F][Kin][G], wB2 [2][F][Kst][F], bias2 [2][F] or NULL, lw2 [2][F*N]
