@@ -158,6 +158,12 @@ class _GatedGCRNNBase(nn.Module):
             sel.append(self.sigma3())
         return nn.Sequential(*sel)
 
+    def _after_head(self, y):
+        """What outputNN holds behind the layer a small-graph launch has evaluated: the finalNonlinearity, where there is one."""
+        for layer in self.outputNN[1:]:
+            y = layer(y)
+        return y
+
 
 class GatedGCRNNforRegression(_GatedGCRNNBase):
     """State cell + MLP head on every h_t (reference architectures.py:1405-1645).
@@ -195,9 +201,7 @@ class GatedGCRNNforRegression(_GatedGCRNNBase):
                 if y is not None:
                     if act is None:
                         y = sigma(y)
-                    for layer in self.outputNN[1:]:                  # finalNonlinearity, where there is one
-                        y = layer(y)
-                    return y
+                    return self._after_head(y)
             # the Selection-GNN head on all B*T states (reference :1630-1632): H [B][T][F_h][N] is already its [items][F][N] input
             H = self.stateGCRNN(x, h0)
             flatY = self.outputNN(H.reshape(-1, self.F_h, self.N))
@@ -222,9 +226,7 @@ class GatedGCRNNforRegression(_GatedGCRNNBase):
             y = self.stateGCRNN.regress(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)      # B x T x O x N
             if y is not None:
                 y = y.reshape(batchSize, seqLength, -1).unsqueeze(2)
-                for layer in self.outputNN[1:]:                      # finalNonlinearity, where there is one
-                    y = layer(y)
-                return y
+                return self._after_head(y)
         H = self.stateGCRNN(x, h0)                                  # B x T x F_h x N
         flatH = H.reshape(-1, self.F_h, self.N)
         if self.mlpType == 'multipMlp':
@@ -265,9 +267,7 @@ class GatedGCRNNforClassification(_GatedGCRNNBase):
             # inside its launch -- neither the T states (inference) nor dH (training) are materialised; None: not that path
             y = self.stateGCRNN.classify(x, h0, self.outputNN[0].weight, self.outputNN[0].bias)
             if y is not None:
-                for layer in self.outputNN[1:]:                      # finalNonlinearity, where there is one
-                    y = layer(y)
-                return y
+                return self._after_head(y)
         if self.gnn_head:
             sel = self.outputNN[0]
             if sel.L == 1 and list(sel.F) == [self.F_h, 1] and len(sel.dimLayersMLP) == 1 and len(sel.MLP) == 1 and \
@@ -279,9 +279,7 @@ class GatedGCRNNforClassification(_GatedGCRNNBase):
                 gfl, lin = sel.GFL[0], sel.MLP[0]
                 y = self.stateGCRNN.classify_gnn(x, h0, gfl.weight, gfl.bias, _FUSED_ACTIVATIONS[type(sel.GFL[1])], lin.weight, lin.bias)
                 if y is not None:
-                    for layer in self.outputNN[1:]:                  # finalNonlinearity, where there is one
-                        y = layer(y)
-                    return y
+                    return self._after_head(y)
         H = self.stateGCRNN(x, h0, last_only=not torch.is_grad_enabled())     # inference: only the last state is materialised
         h = H.select(1, -1)                                          # reference :1844
         if self.gnn_head:

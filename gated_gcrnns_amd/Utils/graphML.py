@@ -730,7 +730,7 @@ class GGCRNNCell(nn.Module):
         recurrence) against batched passes that fill the chip at that length. Those rows are taken off the dispatch here; nothing between
         T = 20 and T = 200 was measured, so fp32 cell inference keeps the composed pass from T = 21 up. GCRNN_SMALL_NODE_GATES=all takes them
         all the same (peak memory 67 against 251 MB and 90 against 422 MB, 7 device events against 35 / 41). train: a backward may follow;
-        head: called for a head inside the launches (_small_head_route)."""
+        head: called for a head inside the launches (_small_linear_head, regress_gnn, classify_gnn)."""
         return train or head or X.dtype != torch.float32 or X.shape[1] <= 20
 
     def _use_small_node_gates(self, X, train, head):
@@ -793,38 +793,56 @@ class GGCRNNCell(nn.Module):
         launch stores the states BPTT reads and makes the logits; the BPTT launch starts from dlogits, so the zero-filled dH [B][T][F][N]
         of `H.select(1, -1)` never exists. Returns logits B x C, or None when this cell / input / head does not run on that path (the
         model then continues on forward()). GCRNN_NO_SMALL_HEAD=1 (read at every call) switches it off: A/B against the two-module path."""
-        route = self._small_head_route(X, h0, weight, bias, 'GCRNN_NO_SMALL_HEAD', lambda w: w.shape[1] == self.F * self.N,
-                                       self._small_last_state_pays, ops.small_head_supported)
-        if route is None:
-            return self._small_edge_head(X, h0, weight, bias, 'GCRNN_NO_SMALL_HEAD', lambda w: w.shape[1] == self.F * self.N,
-                                         ops.SMALL_EDGE_HEAD_LAST, ops.small_edge_cell_classify)
-        return ops.small_cell_classify(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
+        return self._small_linear_head(X, h0, weight, bias, 'GCRNN_NO_SMALL_HEAD', self._readout_weight_ok, self._small_last_state_pays,
+                                       ops.small_head_supported, ops.small_cell_classify, ops.SMALL_EDGE_HEAD_LAST,
+                                       ops.small_edge_cell_classify)
 
-    def _small_head_route(self, X, h0, weight, bias, off_switch, weight_ok, pays, supported):
-        """Whether a head inside the small-graph matrix-core launches takes this cell, input and head (classify, regress): None to decline,
-        else (backward, gi, gf) -- whether the BPTT launch may follow, and the gates as the launches take them. off_switch: the environment
-        variable that declines; weight_ok: the head's test of its 2-D weight; pays: where the inference launch beats the two-module path;
-        supported: the ops query of the head's shapes."""
+    def _small_linear_head(self, X, h0, weight, bias, off_switch, weight_ok, pays, supported, fn, edge_kind, edge_fn):
+        """classify / regress: the head's output from the matrix-core launches (fn), else -- an edge-gated cell -- from _small_edge_head
+        (edge_kind, edge_fn), else None. pays: where the inference launch beats the two-module path, asked once, with `backward` known."""
+        backward = self._small_head_backward(X, h0, weight, bias, off_switch, weight_ok)
+        if backward is not None and (backward or pays(X)) and self._small_head_takes(X, h0, backward, supported, weight.shape[0]):
+            gates = self._small_gates(X, h0, backward, head=True)
+            return fn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, *gates)
+        return self._small_edge_head(X, h0, weight, bias, off_switch, weight_ok, edge_kind, edge_fn)
+
+    # -- what the routes of the heads inside the small-graph launches share (classify, regress, regress_gnn, classify_gnn, _small_edge_head)
+    def _readout_weight_ok(self, w):
+        return w.shape[1] == self.F * self.N
+
+    def _node_weight_ok(self, w):
+        return w.shape[1] == self.F and 0 < w.shape[0] <= 8
+
+    def _small_head_backward(self, X, h0, weight, bias, off_switch, weight_ok, edge=False):
+        """The first half of a route, no device touched: None to decline, else `backward` -- whether a BPTT launch may follow (the cell
+        trains, or the head alone wants a gradient). off_switch: the environment variable that declines, read here at every call;
+        weight_ok: the head's test of its 2-D weight; edge: the cell's own questions are the edge-gated kernels' (_use_small_edge /
+        _use_small_edge_training), else the matrix-core family's (_use_small / _use_small_training)."""
         if os.environ.get(off_switch) or self.graph is None or self._state_padded(X, h0) is not None:
             return None
         if weight.dim() != 2 or not weight_ok(weight) or weight.dtype != X.dtype or (bias is not None and bias.dtype != X.dtype):
             return None
-        gated = self.time_gating == True or self.spatial_gating is not None  # noqa: E712
         head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
-        if self._use_small(X, h0):
-            train = False
-        elif self._use_small_training(X, h0):
-            train = True
-        else:
-            return None
-        backward = train or head_grad
-        if not backward and not pays(X):
-            return None
-        if not supported(self.N, self.G, self.F, self.Kin, self.Kst, weight.shape[0], X.dtype, backward, gated, dx=backward and X.requires_grad):
-            return None
+        if self._use_small_edge(X, h0) if edge else self._use_small(X, h0):
+            return head_grad
+        if self._use_small_edge_training(X, h0) if edge else self._use_small_training(X, h0):
+            return True
+        return None
+
+    def _small_head_on_device(self, X, h0):
+        """The last step of a route that accepts: from here on the device is touched."""
         assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
         ops.require_device(X, h0, self.weight_A)
-        return (backward,) + self._small_gates(X, h0, backward, head=True)
+
+    def _small_head_takes(self, X, h0, backward, supported, *head_shape):
+        """The second half of a matrix-core route: whether `supported` (the ops query of the head's shapes; head_shape: the head's sizes
+        in its order) takes the step, and then that the tensors are where the launches need them. The head's own _pays question is its
+        caller's, asked once with `backward`; what follows a yes is the gates, self._small_gates(X, h0, backward, head=True)."""
+        gated = self.time_gating == True or self.spatial_gating is not None  # noqa: E712
+        if not supported(self.N, self.G, self.F, self.Kin, self.Kst, *head_shape, X.dtype, backward, gated, dx=backward and X.requires_grad):
+            return False
+        self._small_head_on_device(X, h0)
+        return True
 
     @staticmethod
     def _small_edge_head_pays(X, head_kind):
@@ -843,29 +861,17 @@ class GGCRNNCell(nn.Module):
         (_small_edge_head_pays); GCRNN_SMALL_EDGE_HEAD=all takes every supported row. GCRNN_NO_SMALL_EDGE=1 and the head's own off_switch
         win over it. Returns the head's output, or None to decline: the cell must take _use_small_edge (inference) or
         _use_small_edge_training (training, with its GCRNN_SMALL_EDGE_DX rule for an X that wants a gradient), the head the tests of
-        _small_head_route, the shape ops.small_edge_head_supported."""
+        _small_head_backward, the shape ops.small_edge_head_supported."""
         mode = os.environ.get('GCRNN_SMALL_EDGE_HEAD')
-        if not mode or os.environ.get(off_switch) or self.spatial_gating != 'edge':
+        if not mode or self.spatial_gating != 'edge':
             return None
         if mode != 'all' and not self._small_edge_head_pays(X, head_kind):
             return None
-        if self.graph is None or self._state_padded(X, h0) is not None:
+        backward = self._small_head_backward(X, h0, weight, bias, off_switch, weight_ok, edge=True)
+        if backward is None or not ops.small_edge_head_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F,
+                                                                 self.Kin, self.Kst, head_kind, weight.shape[0], X.dtype, backward, self.E):
             return None
-        if weight.dim() != 2 or not weight_ok(weight) or weight.dtype != X.dtype or (bias is not None and bias.dtype != X.dtype):
-            return None
-        head_grad = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
-        if self._use_small_edge(X, h0):
-            train = False
-        elif self._use_small_edge_training(X, h0):
-            train = True
-        else:
-            return None
-        backward = train or head_grad
-        if not ops.small_edge_head_supported(self.N, self.graph.fwd[0].nnz, int(self.graph.mask.nnz), self.G, self.F, self.Kin, self.Kst,
-                                             head_kind, weight.shape[0], X.dtype, backward, self.E):
-            return None
-        assert h0.shape[0] == X.shape[0] and X.shape[2] == self.G and X.shape[3] == self.N
-        ops.require_device(X, h0, self.weight_A)
+        self._small_head_on_device(X, h0)
         gi, gf = self._small_time_gates(X, h0, backward)
         att_in = (self.input_attention.mixer, self.input_attention.weight)
         att_f = (self.forget_attention.mixer, self.forget_attention.weight)
@@ -888,12 +894,9 @@ class GGCRNNCell(nn.Module):
         dH [B][T][F][N] of the two-module path never exists. Returns y B x T x O x N, or None when this cell / input / head does not run on
         that path (the model then continues on forward()). GCRNN_NO_SMALL_NODE_HEAD=1 (read at every call) switches it off: A/B against the
         two-module path."""
-        route = self._small_head_route(X, h0, weight, bias, 'GCRNN_NO_SMALL_NODE_HEAD', lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
-                                       self._small_node_head_pays, ops.small_node_head_supported)
-        if route is None:
-            return self._small_edge_head(X, h0, weight, bias, 'GCRNN_NO_SMALL_NODE_HEAD', lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
-                                         ops.SMALL_EDGE_HEAD_NODE, ops.small_edge_cell_regress)
-        return ops.small_cell_regress(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, weight, bias, route[1], route[2])
+        return self._small_linear_head(X, h0, weight, bias, 'GCRNN_NO_SMALL_NODE_HEAD', self._node_weight_ok, self._small_node_head_pays,
+                                       ops.small_node_head_supported, ops.small_cell_regress, ops.SMALL_EDGE_HEAD_NODE,
+                                       ops.small_edge_cell_regress)
 
     @staticmethod
     def _small_gnn_head_pays(X, backward):
@@ -923,19 +926,24 @@ class GGCRNNCell(nn.Module):
         off: A/B against the two-module path. GCRNN_SMALL_GNN_HEAD=all takes every supported row, also those _small_gnn_head_pays
         leaves to the two-module path (the measurement's own switch)."""
         every = os.environ.get('GCRNN_SMALL_GNN_HEAD') == 'all'
+        taps, bias1 = self._gnn_head_params(weight, bias, act)
+        backward = None if taps is None else self._small_head_backward(X, h0, taps, bias1, 'GCRNN_NO_SMALL_GNN_HEAD', self._node_weight_ok)
+        if backward is None or not self._small_head_takes(X, h0, backward, ops.small_gnn_head_supported, taps.shape[0]):
+            return None
+        if not (every or self._small_gnn_head_pays(X, backward)):
+            return None
+        gates = self._small_gates(X, h0, backward, head=True)
+        return ops.small_cell_regress_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps, bias1, act, *gates)
+
+    def _gnn_head_params(self, weight, bias, act):
+        """(taps [K_o][F], bias [1] or None) of a one-feature graph-filter head as the ops entries take them, from the GraphFilter's
+        F_out x E x K_o x F weight and 1 x 1 bias; (None, None) where it is not such a head (F_out = E = 1, act a key of ops._GFL_ACTS)."""
         if weight.dim() != 4 or weight.shape[0] != 1 or weight.shape[1] != 1 or self.E != 1 or act not in ops._GFL_ACTS:
-            return None
+            return None, None
         if bias is not None and bias.numel() != 1:
-            return None
+            return None, None
         # (a view, not weight[0, 0]: the backward of an index is a zero-fill and a copy per level, four launches a step)
-        taps = weight.reshape(weight.shape[2], weight.shape[3])
-        route = self._small_head_route(X, h0, taps, bias.view(1) if bias is not None else None, 'GCRNN_NO_SMALL_GNN_HEAD',
-                                       lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
-                                       lambda x: every or self._small_gnn_head_pays(x, False), ops.small_gnn_head_supported)
-        if route is None or (route[0] and not every and not self._small_gnn_head_pays(X, True)):
-            return None
-        return ops.small_cell_regress_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps,
-                                          bias.view(1) if bias is not None else None, act, route[1], route[2])
+        return weight.reshape(weight.shape[2], weight.shape[3]), bias.view(1) if bias is not None else None
 
     @staticmethod
     def _small_cls_gnn_head_pays(X, backward):
@@ -964,28 +972,20 @@ class GGCRNNCell(nn.Module):
         forward() + SelectionGNN). GCRNN_NO_SMALL_CLS_GNN_HEAD=1 (read at every call) switches it off: A/B against the two-module path.
         GCRNN_SMALL_CLS_GNN_HEAD=all takes every supported row, also those _small_cls_gnn_head_pays leaves to the two-module path."""
         every = os.environ.get('GCRNN_SMALL_CLS_GNN_HEAD') == 'all'
-        if weight.dim() != 4 or weight.shape[0] != 1 or weight.shape[1] != 1 or self.E != 1 or act not in ops._GFL_ACTS:
-            return None
-        if bias is not None and bias.numel() != 1:
-            return None
-        if self.graph is None or lin_weight.dim() != 2 or lin_weight.shape[1] != self.N or lin_weight.dtype != X.dtype or \
+        taps, bias1 = self._gnn_head_params(weight, bias, act)
+        if taps is None or self.graph is None or lin_weight.dim() != 2 or lin_weight.shape[1] != self.N or lin_weight.dtype != X.dtype or \
                 (lin_bias is not None and lin_bias.dtype != X.dtype):
             return None
-        C = lin_weight.shape[0]
-        # (a view, not weight[0, 0]: see regress_gnn)
-        taps = weight.reshape(weight.shape[2], weight.shape[3])
-        route = self._small_head_route(X, h0, taps, bias.view(1) if bias is not None else None, 'GCRNN_NO_SMALL_CLS_GNN_HEAD',
-                                       lambda w: w.shape[1] == self.F and 0 < w.shape[0] <= 8,
-                                       lambda x: every or self._small_cls_gnn_head_pays(x, False),
-                                       lambda N, G, F, Kin, Kst, K_o, dt, backward, gated, dx=False:
-                                       ops.small_cls_gnn_head_supported(N, G, F, Kin, Kst, K_o, C, dt, backward, gated, dx=dx))
-        if route is None or (route[0] and not every and not self._small_cls_gnn_head_pays(X, True)):
+        backward = self._small_head_backward(X, h0, taps, bias1, 'GCRNN_NO_SMALL_CLS_GNN_HEAD', self._node_weight_ok)
+        if backward is None or not self._small_head_takes(X, h0, backward, ops.small_cls_gnn_head_supported, taps.shape[0],
+                                                          lin_weight.shape[0]):
             return None
         lin_grad = torch.is_grad_enabled() and (lin_weight.requires_grad or (lin_bias is not None and lin_bias.requires_grad))
-        if lin_grad and not route[0]:
-            return None             # only the read-out wants a gradient: the route has asked for an inference launch
-        return ops.small_cell_classify_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps,
-                                           bias.view(1) if bias is not None else None, lin_weight, lin_bias, act, route[1], route[2])
+        if not (every or self._small_cls_gnn_head_pays(X, backward)) or (lin_grad and not backward):
+            return None             # (only the read-out wants a gradient: the shape has been asked for an inference launch)
+        gates = self._small_gates(X, h0, backward, head=True)
+        return ops.small_cell_classify_gnn(X, h0, self.weight_A, self.weight_B, self.bias, self.graph, taps, bias1, lin_weight, lin_bias, act,
+                                           *gates)
 
     # -- fused flagship path (bf16, un-gated / time-gated, sigma = tanh; inference here, training via ops.fused_cell_train) ----
     def _use_fused(self, X, h0):

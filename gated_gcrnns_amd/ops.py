@@ -3214,6 +3214,74 @@ def _small_head_forward(X, h0, wA, wB, bias, graph, head_w, head_b, gi, gf, stor
     return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, store, ('last', head_w, head_b))
 
 
+def _wants_grad(*operands):
+    """Autograd is recording and one of these tensors (None among them: an absent one) wants a gradient."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)
+
+
+def _small_dense_cell_head(fn, head, X, h0, wA, wB, bias, graph, gi, gf):
+    """The one decision of the four matrix-core heads (the edge family's: _small_edge_cell_head): where nothing wants a gradient the
+    inference launch that stores no state, else the autograd node fn. head: _small_dense_forward's tuple, which names the head's
+    parameters -- (kind, head_w, head_b[, act[, lin_w, lin_b, None]]); fn takes them in that order, then graph, then act."""
+    params, act = head[1:3] + head[4:6], head[3:4]
+    require_device(X, h0, wA, wB, bias, *params[::2])                 # (the weights; a bias lives where its weight does)
+    if not _wants_grad(X, h0, wA, wB, bias, gi, gf, *params):
+        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, head)[1]
+    return fn.apply(X, h0, wA, wB, bias, gi, gf, *params, graph, *act)
+
+
+def _small_dense_head_bptt(ctx, entry, supported, head_shape, seed):
+    """The backward of every matrix-core head node up to its own parameters: the dx question (supported, the node's shape query, with
+    head_shape = (C,), (O,), (K_o,) or (K_o, C); entry: the public function the error names) and the one BPTT launch on what the forward
+    saved, (dX, dh0, dwA, dwB, db, dgi, dgf). seed: _small_dense_bptt's (a seed that costs a launch, the graph-filter head's adjoint,
+    has been issued by then: the route has asked the same question before the forward, so the error is a direct caller's)."""
+    X, h0, H, wA, wB, bias, gi, gf = ctx.saved_tensors[:8]
+    want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if want_dx and not supported(X.shape[3], X.shape[2], wA.shape[0], wA.shape[2], wB.shape[2], *head_shape, X.dtype, True, gi is not None,
+                                 dx=True):
+        raise GcrnnError('%s: no gradient for X at this shape (%s with dx)' % (entry, supported.__name__))
+    return _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, seed)
+
+
+def _readout_grads(dlogits, h, want_w, want_b):
+    """The own gradients of a read-out Linear on items h [B][...] from dlogits [B][C]: (d w = dlogits^T h [C][...flat] or None, d b, its
+    column sums, or None). Library glue."""
+    return (dlogits.t().mm(h.reshape(h.shape[0], -1)) if want_w else None, dlogits.sum(dim=0) if want_b else None)
+
+
+def _node_head_grads(H, dU, w, want_w, want_b, bias_kernel, bias_level0):
+    """The own gradients of a per-node linear head w [O][F] (contiguous) on the items H [R][F][N], from dU [R][O][N] (contiguous):
+    (d w[o][f] = sum_{r,n} dU[r][o][n] H[r][f][n] or None, the bias gradient or None). No [R][F][N] temporary is made. The items: every
+    stored state as it lies (R = B T), or a view of the last one (R = B), copied for the kernel. bias_kernel: the kernel also runs where
+    the bias alone wants a gradient (the graph-filter heads), else that case is a sum of dU (the per-node heads). bias_level0: the bias
+    gradient is level 0's sum alone, [1] (a graph filter's one bias), else all O column sums.
+
+    The kernel is node_linear's own backward with dh = NULL: one pass over H and dU into per-block slots. The batched library product
+    does the same in 20000 GEMMs of one row at B T = 20000 and measured 375 us against this kernel's 102 us WITH its dh store (fp32, the
+    k-step driver's shape, T = 200: DESIGN 4.12); on R = B an einsum is ONE fp64 GEMM of 4 x 20 outputs over a contraction of B N = 5900
+    -- a single serial tile, 0.13 ms of device time per step. Every operand of the launch is a named local of this frame
+    (_small_dense_bptt), the copy of the last state included."""
+    R, F, N = H.shape
+    O, dt = dU.shape[1], H.dtype
+    dw = db = None
+    if (want_w or (bias_kernel and want_b)) and node_linear_supported(F, O, dt):
+        Hc = H.contiguous()
+        nblk = int(lib.gcrnn_node_linear_blocks(R, N))
+        pw = torch.empty((nblk, O, F), dtype=dt, device=H.device)
+        pb = torch.empty((nblk, O), dtype=dt, device=H.device)
+        check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(Hc), _p(w), _p(dU), None, _p(pw), _p(pb), R, N, F, O, _stream()),
+              'node_linear_backward')
+        dw = pw.sum(dim=0) if want_w else None
+        if want_b:
+            db = pb[:, 0].sum(dim=0).view(1) if bias_level0 else pb.sum(dim=0)
+    else:
+        if want_w:                                        # F beyond node_linear's kernel: a batched product on views, [R][O][F] its only temporary
+            dw = torch.bmm(dU, H.transpose(1, 2)).sum(0)
+        if want_b:
+            db = dU[:, 0].sum().view(1) if bias_level0 else dU.sum(dim=(0, 2))
+    return dw, db
+
+
 class _SmallCellHead(torch.autograd.Function):
     """Small-graph cell + Linear(F N -> C) on its last state as ONE autograd node. Forward: one launch that stores every state (BPTT
     reads them) and makes the logits. Backward: one BPTT launch seeded from dlogits inside the kernel (gcrnn_small_dense_backward_head:
@@ -3229,18 +3297,11 @@ class _SmallCellHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        X, h0, H, wA, wB, bias, gi, gf, head_w = ctx.saved_tensors
-        B, T, G, N = X.shape
-        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
-        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if want_dx and not small_head_supported(N, G, F, Kin, Kst, head_w.shape[0], X.dtype, True, gi is not None, dx=True):
-            raise GcrnnError('small_cell_classify: no gradient for X at this shape (small_head_supported with dx)')
+        H, head_w = ctx.saved_tensors[2], ctx.saved_tensors[8]
         dlc = dlogits.contiguous()
-        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0,
-                                  ('dlogits', dlc, head_w.detach().contiguous()))
-        dhw = dlc.t().mm(H[:, -1].reshape(B, F * N)) if ctx.needs_input_grad[7] else None
-        dhb = dlc.sum(dim=0) if ctx.has_hb and ctx.needs_input_grad[8] else None
-        return grads + (dhw, dhb, None)
+        grads = _small_dense_head_bptt(ctx, 'small_cell_classify', small_head_supported, (head_w.shape[0],),
+                                       ('dlogits', dlc, head_w.detach().contiguous()))
+        return grads + _readout_grads(dlc, H[:, -1], ctx.needs_input_grad[7], ctx.has_hb and ctx.needs_input_grad[8]) + (None,)
 
 
 def small_cell_classify(X, h0, wA, wB, bias, graph, head_w, head_b, gi=None, gf=None):
@@ -3248,11 +3309,7 @@ def small_cell_classify(X, h0, wA, wB, bias, graph, head_w, head_b, gi=None, gf=
     logits [B][C]. Where nothing wants a gradient it is one launch that stores no state; otherwise one autograd node (_SmallCellHead)
     with gradients for X (only where wanted: small_head_supported with dx), h0, the taps, the bias, the gates and the head. Shapes:
     small_head_supported."""
-    require_device(X, h0, wA, wB, bias, head_w)
-    operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
-        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('last', head_w, head_b))[1]
-    return _SmallCellHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph)
+    return _small_dense_cell_head(_SmallCellHead, ('last', head_w, head_b), X, h0, wA, wB, bias, graph, gi, gf)
 
 
 # ---- the regression model on the matrix-core kernels: per-node head Linear(F -> O) on every state inside the two launches
@@ -3289,35 +3346,13 @@ class _SmallCellNodeHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        X, h0, H, wA, wB, bias, gi, gf, node_w = ctx.saved_tensors
-        B, T, G, N = X.shape
-        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        H, node_w = ctx.saved_tensors[2], ctx.saved_tensors[8]
+        B, T, F, N = H.shape
         O = node_w.shape[0]
-        dt, dev = X.dtype, X.device
-        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if want_dx and not small_node_head_supported(N, G, F, Kin, Kst, O, dt, True, gi is not None, dx=True):
-            raise GcrnnError('small_cell_regress: no gradient for X at this shape (small_node_head_supported with dx)')
         dYc, nw = dY.contiguous(), node_w.detach().contiguous()
-        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dY', dYc, nw))
-        # d node_w[o][f] = sum_{b,t,n} dY[b][t][o][n] H[b][t][f][n] and d node_b[o] = sum dY: neither makes a [B][T][F][N] temporary
-        dnw = dnb = None
-        want_nb = ctx.has_nb and ctx.needs_input_grad[8]
-        if ctx.needs_input_grad[7] and node_linear_supported(F, O, dt):
-            # node_linear's own backward kernel with dh = NULL: one pass over H and dY into per-block slots. The batched library product
-            # below does the same in 20000 GEMMs of one row at B T = 20000 and measured 375 us against this kernel's 102 us WITH its dh store
-            # (fp32, the k-step driver's shape, T = 200: DESIGN 4.12)
-            nblk = int(lib.gcrnn_node_linear_blocks(B * T, N))
-            pw = torch.empty((nblk, O, F), dtype=dt, device=dev)
-            pnb = torch.empty((nblk, O), dtype=dt, device=dev)
-            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(H), _p(nw), _p(dYc), None, _p(pw), _p(pnb), B * T, N, F, O, _stream()),
-                  'node_linear_backward')
-            dnw = pw.sum(dim=0)
-            dnb = pnb.sum(dim=0) if want_nb else None
-        else:
-            if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B T][O][F] its only temporary
-                dnw = torch.bmm(dYc.view(B * T, O, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
-            dnb = dYc.sum(dim=(0, 1, 3)) if want_nb else None
-        return grads + (dnw, dnb, None)
+        grads = _small_dense_head_bptt(ctx, 'small_cell_regress', small_node_head_supported, (O,), ('dY', dYc, nw))
+        return grads + _node_head_grads(H.view(B * T, F, N), dYc.view(B * T, O, N), nw, ctx.needs_input_grad[7],
+                                        ctx.has_nb and ctx.needs_input_grad[8], bias_kernel=False, bias_level0=False) + (None,)
 
 
 def small_cell_regress(X, h0, wA, wB, bias, graph, node_w, node_b, gi=None, gf=None):
@@ -3325,11 +3360,7 @@ def small_cell_regress(X, h0, wA, wB, bias, graph, node_w, node_b, gi=None, gf=N
     dtype): Y [B][T][O][N]. Where nothing wants a gradient it is one launch that stores no state; otherwise one autograd node
     (_SmallCellNodeHead) with gradients for X (only where wanted: small_node_head_supported with dx), h0, the taps, the bias, the gates
     and the head. Shapes: small_node_head_supported."""
-    require_device(X, h0, wA, wB, bias, node_w)
-    operands = (X, h0, wA, wB, bias, gi, gf, node_w, node_b)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
-        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('node', node_w, node_b))[1]
-    return _SmallCellNodeHead.apply(X, h0, wA, wB, bias, gi, gf, node_w, node_b, graph)
+    return _small_dense_cell_head(_SmallCellNodeHead, ('node', node_w, node_b), X, h0, wA, wB, bias, graph, gi, gf)
 
 
 # ---- the regression model's Selection-GNN head on the matrix-core kernels: GraphFilter(F -> 1, K_o) + activation on every state inside the
@@ -3376,32 +3407,14 @@ class _SmallCellGnnHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        X, h0, H, wA, wB, bias, gi, gf, head_w, Y = ctx.saved_tensors
-        B, T, G, N = X.shape
-        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
+        H, head_w, Y = ctx.saved_tensors[2], ctx.saved_tensors[8], ctx.saved_tensors[9]
+        B, T, F, N = H.shape
         Ko = head_w.shape[0]
-        dt, dev = X.dtype, X.device
-        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if want_dx and not small_gnn_head_supported(N, G, F, Kin, Kst, Ko, dt, True, gi is not None, dx=True):
-            raise GcrnnError('small_cell_regress_gnn: no gradient for X at this shape (small_gnn_head_supported with dx)')
-        dU, hw = small_gnn_head_adjoint(dY.to(dt), Y, ctx.graph, Ko, ctx.act), head_w.detach().contiguous()
-        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dY', dU, hw))
-        # d head_w[k][f] = sum_{b,t,n} dU[b][t][k][n] H[b][t][f][n] and d head_b = sum dU_0: the per-node head's sums with O = K_o
-        dhw = dhb = None
-        want_hb = ctx.has_hb and ctx.needs_input_grad[8]
-        if (ctx.needs_input_grad[7] or want_hb) and node_linear_supported(F, Ko, dt):
-            nblk = int(lib.gcrnn_node_linear_blocks(B * T, N))
-            pw = torch.empty((nblk, Ko, F), dtype=dt, device=dev)
-            pnb = torch.empty((nblk, Ko), dtype=dt, device=dev)
-            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(H), _p(hw), _p(dU), None, _p(pw), _p(pnb), B * T, N, F, Ko, _stream()),
-                  'node_linear_backward')
-            dhw = pw.sum(dim=0) if ctx.needs_input_grad[7] else None
-            dhb = pnb[:, 0].sum(dim=0).view(1) if want_hb else None
-        else:
-            if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B T][K_o][F] its only temporary
-                dhw = torch.bmm(dU.view(B * T, Ko, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
-            dhb = dU[:, :, 0].sum().view(1) if want_hb else None
-        return grads + (dhw, dhb, None, None)
+        dU, hw = small_gnn_head_adjoint(dY.to(H.dtype), Y, ctx.graph, Ko, ctx.act), head_w.detach().contiguous()
+        grads = _small_dense_head_bptt(ctx, 'small_cell_regress_gnn', small_gnn_head_supported, (Ko,), ('dY', dU, hw))
+        # the per-node head's sums with O = K_o on (H, dU); the bias is level 0's
+        return grads + _node_head_grads(H.view(B * T, F, N), dU.view(B * T, Ko, N), hw, ctx.needs_input_grad[7],
+                                        ctx.has_hb and ctx.needs_input_grad[8], bias_kernel=True, bias_level0=True) + (None, None)
 
 
 def small_cell_regress_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, act=None, gi=None, gf=None):
@@ -3412,11 +3425,7 @@ def small_cell_regress_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, act=None,
     (_SmallCellGnnHead) with gradients for X (only where wanted: small_gnn_head_supported with dx), h0, the taps, the bias, the gates and
     the head. Shapes: small_gnn_head_supported."""
     assert act in _GFL_ACTS, act
-    require_device(X, h0, wA, wB, bias, head_w)
-    operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
-        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE, ('gnn', head_w, head_b, act))[1]
-    return _SmallCellGnnHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, graph, act)
+    return _small_dense_cell_head(_SmallCellGnnHead, ('gnn', head_w, head_b, act), X, h0, wA, wB, bias, graph, gi, gf)
 
 
 # ---- the classification model's Selection-GNN head on the matrix-core kernels: GraphFilter(F -> 1, K_o) + activation + Linear(N -> C) on
@@ -3452,39 +3461,17 @@ class _SmallCellClsGnnHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        X, h0, H, wA, wB, bias, gi, gf, head_w, lin_w, V = ctx.saved_tensors
-        B, T, G, N = X.shape
-        F, Kin, Kst = wA.shape[0], wA.shape[2], wB.shape[2]
-        Ko, C = head_w.shape[0], lin_w.shape[0]
-        dt, dev = X.dtype, X.device
-        want_dx, want_dh0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if want_dx and not small_cls_gnn_head_supported(N, G, F, Kin, Kst, Ko, C, dt, True, gi is not None, dx=True):
-            raise GcrnnError('small_cell_classify_gnn: no gradient for X at this shape (small_cls_gnn_head_supported with dx)')
+        H, head_w, lin_w, V = ctx.saved_tensors[2], ctx.saved_tensors[8], ctx.saved_tensors[9], ctx.saved_tensors[10]
+        B, N, Ko, C, dt = V.shape[0], V.shape[1], head_w.shape[0], lin_w.shape[0], H.dtype
         dlc, hw, lw = dlogits.to(dt).contiguous(), head_w.detach().contiguous(), lin_w.detach().contiguous()
-        dU = torch.empty((B, Ko, N), dtype=dt, device=dev)
-        grads = _small_dense_bptt(X, h0, H, wA, wB, bias, gi, gf, ctx.graph, want_dx, want_dh0, ('dcls', dlc, hw, lw, V, ctx.act, dU))
-        # d head_w[k][f] = sum_{b,n} dU[b][k][n] h_T[b][f][n] and d head_b = sum dU_0: the per-node head's sums with O = K_o on B items,
-        # through node_linear's backward kernel with dh = NULL on a contiguous copy of the last state ([B][F][N]; no buffer with a T in its
-        # shape). An einsum here is ONE fp64 GEMM of 4 x 20 outputs over a contraction of B N = 5900 -- a single serial tile, measured at
-        # 0.13 ms of device time per step. d lin_w = dlogits^T V, d lin_b its column sums, as the MLP heads everywhere
-        dhw = dhb = None
-        want_hb = ctx.has_hb and ctx.needs_input_grad[8]
-        if (ctx.needs_input_grad[7] or want_hb) and node_linear_supported(F, Ko, dt):
-            hT = H[:, -1].contiguous()
-            nblk = int(lib.gcrnn_node_linear_blocks(B, N))
-            pw = torch.empty((nblk, Ko, F), dtype=dt, device=dev)
-            pnb = torch.empty((nblk, Ko), dtype=dt, device=dev)
-            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(hT), _p(hw), _p(dU), None, _p(pw), _p(pnb), B, N, F, Ko, _stream()),
-                  'node_linear_backward')
-            dhw = pw.sum(dim=0) if ctx.needs_input_grad[7] else None
-            dhb = pnb[:, 0].sum(dim=0).view(1) if want_hb else None
-        else:
-            if ctx.needs_input_grad[7]:                   # F beyond node_linear's kernel: a batched product on views, [B][K_o][F] its only temporary
-                dhw = torch.bmm(dU, H[:, -1].transpose(1, 2)).sum(0)
-            dhb = dU[:, 0].sum().view(1) if want_hb else None
-        dlw = dlc.t().mm(V) if ctx.needs_input_grad[9] else None
-        dlb = dlc.sum(dim=0) if ctx.has_lb and ctx.needs_input_grad[10] else None
-        return grads + (dhw, dhb, dlw, dlb, None, None)
+        dU = torch.empty((B, Ko, N), dtype=dt, device=H.device)
+        grads = _small_dense_head_bptt(ctx, 'small_cell_classify_gnn', small_cls_gnn_head_supported, (Ko, C),
+                                       ('dcls', dlc, hw, lw, V, ctx.act, dU))
+        # the per-node head's sums with O = K_o on the B items of the last state (no buffer with a T in its shape), the bias level 0's;
+        # d lin_w = dlogits^T V, d lin_b its column sums, as the MLP heads everywhere
+        need = ctx.needs_input_grad
+        return grads + _node_head_grads(H[:, -1], dU, hw, need[7], ctx.has_hb and need[8], bias_kernel=True, bias_level0=True) + \
+            _readout_grads(dlc, V, need[9], ctx.has_lb and need[10]) + (None, None)
 
 
 def small_cell_classify_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, lin_w, lin_b, act=None, gi=None, gf=None):
@@ -3495,12 +3482,8 @@ def small_cell_classify_gnn(X, h0, wA, wB, bias, graph, head_w, head_b, lin_w, l
     is one launch that stores no state; otherwise one autograd node (_SmallCellClsGnnHead) with gradients for X (only where wanted:
     small_cls_gnn_head_supported with dx), h0, the taps, the bias, the gates and the head. Shapes: small_cls_gnn_head_supported."""
     assert act in _GFL_ACTS, act
-    require_device(X, h0, wA, wB, bias, head_w, lin_w)
-    operands = (X, h0, wA, wB, bias, gi, gf, head_w, head_b, lin_w, lin_b)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
-        return _small_dense_forward(X, h0, wA, wB, bias, graph, gi, gf, SMALL_STATES_NONE,
-                                    ('cls_gnn', head_w, head_b, act, lin_w, lin_b, None))[1]
-    return _SmallCellClsGnnHead.apply(X, h0, wA, wB, bias, gi, gf, head_w, head_b, lin_w, lin_b, graph, act)
+    return _small_dense_cell_head(_SmallCellClsGnnHead, ('cls_gnn', head_w, head_b, act, lin_w, lin_b, None), X, h0, wA, wB, bias, graph,
+                                  gi, gf)
 
 
 def small_gates_supported(N, G, F, Kin, Kst, dtype, backward):
@@ -3879,13 +3862,10 @@ class _SmallEdgeCellHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        X, H, head_w = ctx.saved_tensors[0], ctx.saved_tensors[2], ctx.saved_tensors[12]
-        B, F, N = X.shape[0], H.shape[2], H.shape[3]
+        H, head_w = ctx.saved_tensors[2], ctx.saved_tensors[12]
         dlc, hw = dlogits.contiguous(), head_w.detach().contiguous()
         grads = _small_edge_bptt_head(ctx, SMALL_EDGE_HEAD_LAST, dlc, hw)
-        dhw = dlc.t().mm(H[:, -1].reshape(B, F * N)) if ctx.needs_input_grad[11] else None
-        dhb = dlc.sum(dim=0) if ctx.has_hb and ctx.needs_input_grad[12] else None
-        return grads + (dhw, dhb, None)
+        return grads + _readout_grads(dlc, H[:, -1], ctx.needs_input_grad[11], ctx.has_hb and ctx.needs_input_grad[12]) + (None,)
 
 
 class _SmallEdgeCellNodeHead(torch.autograd.Function):
@@ -3905,34 +3885,18 @@ class _SmallEdgeCellNodeHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        X, H, node_w = ctx.saved_tensors[0], ctx.saved_tensors[2], ctx.saved_tensors[12]
+        H, node_w = ctx.saved_tensors[2], ctx.saved_tensors[12]
         B, T, F, N = H.shape
         O = node_w.shape[0]
-        dt, dev = X.dtype, X.device
         dYc, nw = dY.contiguous(), node_w.detach().contiguous()
         grads = _small_edge_bptt_head(ctx, SMALL_EDGE_HEAD_NODE, dYc, nw)
-        dnw = dnb = None
-        want_nb = ctx.has_nb and ctx.needs_input_grad[12]
-        if ctx.needs_input_grad[11] and node_linear_supported(F, O, dt):
-            # node_linear's own backward kernel with dh = NULL: one pass over H and dY into per-block slots (_SmallCellNodeHead)
-            nblk = int(lib.gcrnn_node_linear_blocks(B * T, N))
-            pw = torch.empty((nblk, O, F), dtype=dt, device=dev)
-            pnb = torch.empty((nblk, O), dtype=dt, device=dev)
-            check(lib.gcrnn_node_linear_backward(dtype_code(dt), _p(H), _p(nw), _p(dYc), None, _p(pw), _p(pnb), B * T, N, F, O, _stream()),
-                  'node_linear_backward')
-            dnw = pw.sum(dim=0)
-            dnb = pnb.sum(dim=0) if want_nb else None
-        else:
-            if ctx.needs_input_grad[11]:                  # F beyond node_linear's kernel: a batched product on views
-                dnw = torch.bmm(dYc.view(B * T, O, N), H.view(B * T, F, N).transpose(1, 2)).sum(0)
-            dnb = dYc.sum(dim=(0, 1, 3)) if want_nb else None
-        return grads + (dnw, dnb, None)
+        return grads + _node_head_grads(H.view(B * T, F, N), dYc.view(B * T, O, N), nw, ctx.needs_input_grad[11],
+                                        ctx.has_nb and ctx.needs_input_grad[12], bias_kernel=False, bias_level0=False) + (None,)
 
 
 def _small_edge_cell_head(fn, head_kind, X, h0, wA, wB, bias, graph, att_in, att_f, head_w, head_b, gi, gf):
     require_device(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], head_w)
-    operands = (X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, head_w, head_b)
-    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in operands)):
+    if not _wants_grad(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, head_w, head_b):
         return _small_edge_forward_head(X, h0, wA, wB, bias, graph, att_in, att_f, gi, gf, head_kind, head_w, head_b, SMALL_STATES_NONE)[1]
     return fn.apply(X, h0, wA, wB, bias, att_in[0], att_in[1], att_f[0], att_f[1], gi, gf, head_w, head_b, graph)
 
